@@ -10,8 +10,15 @@ the launch stream; ``--secondary-bucket`` times B batches per collective beside 
 Weak scaling: every rank owns ``--tuples-per-gpu``
 tuples (default 2**28, BASELINE configs[2]) of one global splitmix64 stream.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run places the buffers, settles, warms up, times the K steps and prints the line of
+that headline measurement alone.  ``--full`` adds everything else the line can carry: the CPU
+baseline, the per-launch spread, the check of the timed work against the oracle's digests, the
+``bucketed`` / ``configs3`` / ``configs4`` blocks, the counts-only, u32-queue and flow-like
+lines and the row-f kernels.  ``--dump-outputs DIR`` writes what the last timed step computed
+as ``DIR/<name>.npy``.
 
 Rank 0 prints ONE JSON line (see DESIGN.md §5 for every field).
 """
@@ -107,6 +114,17 @@ def parse_args():
     p.add_argument("--no-verify", action="store_true",
                    help="skip the untimed check of the timed work against "
                         "tests/golden/bench_digest.npz")
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline measurement also run the CPU baseline, the "
+                        "per-launch spread, the verification against the oracle's digests, the "
+                        "bucketed / configs[3] / configs[4] blocks, the counts-only, u32-queue "
+                        "and flow-like lines and the row-f kernels (off: the timed steps alone)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step computed on rank "
+                        "0 as DIR/<name>.npy: counts (the reduced per-queue counts, float64), "
+                        "hash_result (float64) and queue_number (float32) of the rank's shard "
+                        "-- of every tuple up to 2**21 tuples, else of a fixed seeded sample of "
+                        "2**21 tuple indices in ascending order")
     return p.parse_args()
 
 
@@ -358,6 +376,34 @@ def golden_counts(gold, first, n):
     if first % C or n % C or first + n > int(gold["total"]):
         return None
     return [int(v) for v in gold["counts"][first // C:(first + n) // C].sum(axis=0)]
+
+
+DUMP_SAMPLE = 1 << 21   # tuples per dumped per-tuple output: 16 + 8 MiB of .npy in all
+
+
+def dump_outputs(torch, out_dir, hashes, queues, counts):
+    """``--dump-outputs``: what a caller of the timed step receives, as ``<name>.npy`` under
+    ``out_dir`` -- ``counts`` (the step's reduced per-queue counts), ``hash_result`` (the int32
+    view of the resident u32 hashes) and ``queue_number`` (``ResidentBatch.queue_view()``), in
+    float64 / float64 / float32 (float64 for u32 queues), which hold every u64 count below
+    2^53, u32 hash and u8 / u16 queue exactly.  More than DUMP_SAMPLE tuples: the outputs at DUMP_SAMPLE tuple indices
+    drawn by ``numpy.random.default_rng(SEED)``, ascending -- the same indices in every run."""
+    import numpy as np
+    n = hashes.numel()
+    os.makedirs(out_dir, exist_ok=True)
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(SEED).integers(0, n, DUMP_SAMPLE))
+        idx = torch.from_numpy(idx).to(hashes.device)
+        hashes, queues = hashes[idx], queues[idx]
+    h = hashes.cpu().numpy().view(np.uint32)
+    q = queues.cpu().numpy()
+    if q.dtype != np.uint8:  # int16 / int32 views of u16 / u32 queues
+        q = q.view(np.uint16 if q.dtype == np.int16 else np.uint32)
+    c = counts.cpu().numpy().view(np.uint64)
+    np.save(os.path.join(out_dir, "counts.npy"), c.astype(np.float64))
+    np.save(os.path.join(out_dir, "hash_result.npy"), h.astype(np.float64))
+    np.save(os.path.join(out_dir, "queue_number.npy"),
+            q.astype(np.float32 if queues.dtype != torch.int32 else np.float64))
 
 
 def _okcode(v):
@@ -748,17 +794,9 @@ def build_line(args, m):
             "kernel_ms": kernel_ms_max,
             "kernel_ms_rank0": m["kernel_ms"],
             "kernel_ms_max_rank": kernel_ms_max,
-            "kernel_ms_min_max": [launch_ms[0], launch_ms[-1]],
-            "kernel_ms_median": launch_ms[len(launch_ms) // 2],
-            "kernel_ms_events_mean": sum(launch_ms) / len(launch_ms),
             "timing": "kernel_ms = GPU time per step on the launch stream: one pair of HIP "
                       "events around the %d timed launches (launches + the gaps between "
-                      "them), slowest rank (kernel_ms_max_rank); min_max / median / "
-                      "events_mean: %d launches each bracketed by HIP events, after the "
-                      "timed region (RSS_FLAG_ADDR64: the 64-bit instance, like the probe, "
-                      "settle and flow-like launches; the step's 32-bit instance runs only "
-                      "the warmup and timed launches)"
-                      % (args.steps, args.steps),
+                      "them), slowest rank (kernel_ms_max_rank)" % args.steps,
         },
         # the HBM-read roofline is the counts-only mode's bound (12 B read
         # per tuple, 666.7 G tuples/s per GPU); the full-output `value` also writes
@@ -766,27 +804,43 @@ def build_line(args, m):
         # HBM use (roofline.frac is its own algorithmic-byte fraction)
         "hbm_read_roofline": {
             "bound_tuples_per_s_per_gpu": HBM_PEAK_GBS * 1e9 / READ_BYTES,
-            "counts_only_frac": n / (co_ms / 1e3) / (HBM_PEAK_GBS * 1e9 / READ_BYTES),
             "full_value_frac": value / (world * HBM_PEAK_GBS * 1e9 / READ_BYTES),
             # the same for the full-output kernel alone (slowest rank's mean launch), i.e.
             # without the per-step counts zeroing, event records and launch gaps
             "full_kernel_frac": n / (kernel_ms_max / 1e3) / (HBM_PEAK_GBS * 1e9 / READ_BYTES),
         },
-        "counts_only": {
+        "cpu_baseline": m["baseline"],
+        "full": bool(args.full),
+    }
+    # the blocks below are measured by --full runs only (launches of their own after the
+    # timed region)
+    if launch_ms is not None:
+        line["roofline"].update({
+            "kernel_ms_min_max": [launch_ms[0], launch_ms[-1]],
+            "kernel_ms_median": launch_ms[len(launch_ms) // 2],
+            "kernel_ms_events_mean": sum(launch_ms) / len(launch_ms),
+            "timing": line["roofline"]["timing"] +
+                      "; min_max / median / events_mean: %d launches each bracketed by HIP "
+                      "events, after the timed region (RSS_FLAG_ADDR64: the 64-bit instance, "
+                      "like the probe, settle and flow-like launches; the step's 32-bit "
+                      "instance runs only the warmup and timed launches)" % args.steps})
+    if co_ms is not None:
+        line["hbm_read_roofline"]["counts_only_frac"] = \
+            n / (co_ms / 1e3) / (HBM_PEAK_GBS * 1e9 / READ_BYTES)
+        line["counts_only"] = {
             "kernel_ms": co_ms,
             "input_probe_ms": m["co_probe"],
             "tuples_per_s_per_gpu": n / (co_ms / 1e3),
             "hbm_read_GBs": n * READ_BYTES / (co_ms / 1e3) / 1e9,
             "hbm_read_frac": n * READ_BYTES / (co_ms / 1e3) / 1e9 / HBM_PEAK_GBS,
-        },
-        "queue_u32": {
+        }
+    if u32_ms is not None:
+        line["queue_u32"] = {
             "kernel_ms": u32_ms,
             "queue_buffer_probe_ms": m["u32_probe"],
             "tuples_per_s_per_gpu": n / (u32_ms / 1e3),
             "achieved_GBs": n * 20 / (u32_ms / 1e3) / 1e9,
-        },
-        "cpu_baseline": m["baseline"],
-    }
+        }
     line["secondary_min_median_max_ms"] = m["secondary_spread"]
     line["settle"] = {"launches": m["settle_launches"], "s": round(m["settle_s"], 3),
                       "note": "untimed launches of the step before the warmup steps "
@@ -850,10 +904,10 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     key_bytes = [int(x, 16) for x in EXAMPLE_KEY.split(":")]
 
-    # rank 0 times the CPU baseline at every world size, before it (or any rank) joins the
-    # process group or touches the GPU: the other ranks wait in the rendezvous meanwhile
+    # --full: rank 0 times the CPU baseline at every world size, before it (or any rank) joins
+    # the process group or touches the GPU: the other ranks wait in the rendezvous meanwhile
     baseline = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         procs = args.cpu_procs or cpu_share()
         baseline = cpu_baseline(key_bytes, args.cpu_sample or max(20000, 1500 * procs), procs,
                                 args.distribution)
@@ -1044,18 +1098,22 @@ def main():
     if total != n * world:
         raise SystemExit("bench: per-queue counts sum to %d, expected %d" % (total, n * world))
     kernel_ms = region[0].elapsed_time(region[1]) / args.steps
-    # per-launch spread: K launches of the same step, each bracketed by its own events --
-    # with RSS_FLAG_ADDR64 (same access shape, the 64-bit instance) like every untimed
+    if args.dump_outputs and rank == 0:  # the last timed step's outputs, before anything else
+        dump_outputs(torch, args.dump_outputs, hashes, batch.queue_view(), last)
+    # --full, per-launch spread: K launches of the same step, each bracketed by its own events
+    # -- with RSS_FLAG_ADDR64 (same access shape, the 64-bit instance) like every untimed
     # launch of the step, so a profile's row for the step's 32-bit instance holds exactly
     # the W warmup + K timed launches
-    spread_ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                 for _ in range(args.steps)]
-    for e in spread_ev:
-        e[0].record(stream)
-        launch(counts, workspace=pipeline.workspace, extra_flags=_native.FLAG_ADDR64)
-        e[1].record(stream)
-    torch.cuda.synchronize()
-    launch_ms = sorted(a.elapsed_time(b) for a, b in spread_ev)
+    launch_ms = None
+    if args.full:
+        spread_ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                     for _ in range(args.steps)]
+        for e in spread_ev:
+            e[0].record(stream)
+            launch(counts, workspace=pipeline.workspace, extra_flags=_native.FLAG_ADDR64)
+            e[1].record(stream)
+        torch.cuda.synchronize()
+        launch_ms = sorted(a.elapsed_time(b) for a, b in spread_ev)
     red_dev = dev if args.dist_backend == "nccl" else "cpu"
 
     def reduce_max(values):
@@ -1066,7 +1124,7 @@ def main():
     # The timed work itself, checked after the timed region (untimed): the resident outputs
     # of this rank's shard against the C oracle's per-block digests and the reduced counts
     # against the oracle's (tests/golden/make_bench_digest.py; simulator.py:94-113).
-    gold = None if args.no_verify else load_digest()
+    gold = None if args.no_verify or not args.full else load_digest()
     verify_ok = digest_applies(gold, key_bytes, H, Q, args.distribution)
     verified = {"main": None, "configs3": None}
     if verify_ok:
@@ -1080,7 +1138,7 @@ def main():
     # collective (CountsPipeline(bucket=B)) -- fewer exchanges than the reference's one
     # histogram per batch, so never the `value`
     bucketed = None
-    if distributed and args.secondary_bucket > 1:
+    if args.full and distributed and args.secondary_bucket > 1:
         bpipe = CountsPipeline(Q, dev, single_pass=not args.zero_counts, htable=H,
                                allreduce=args.allreduce, comm=comm, bucket=args.secondary_bucket)
         bucketed = run_bucketed(bpipe, launch, args.steps, args.warmup, barrier,
@@ -1092,7 +1150,7 @@ def main():
     # (bucket 1) -- the reference's unit of work, one histogram per batch
     # (simulator.py:100-116) -- strong scaling over N.
     c3 = None
-    if args.configs3_tuples > 0:
+    if args.full and args.configs3_tuples > 0:
         c3 = run_configs3(args, torch, dist, _native, dev, stream, key, comm, rank, world,
                           distributed, barrier, qw, probe, gold if verify_ok else None)
         verified["configs3"] = c3.pop("verified")
@@ -1107,8 +1165,8 @@ def main():
 
     # secondary lines (rank 0, after the timed region): counts-only mode (12 B/tuple,
     # the HBM-read roofline) and u32 queue outputs (20 B/tuple)
-    co_ms = u32_ms = flow_ms = configs4 = None
-    if rank == 0:
+    co_ms = u32_ms = flow_ms = configs4 = co_probe = u32_probe = None
+    if args.full and rank == 0:
         reps = max(5, args.steps // 2)
         # counts only reads its input alone, and the read rate also depends a little on the
         # input's placement (profiles/r02/co_placed_probe.log): a counts-only deployment places
@@ -1167,7 +1225,7 @@ def main():
                                    qflag | _native.FLAG_ADDR64, reps)
 
     extras = None
-    if rank == 0 and not args.no_extras:
+    if args.full and rank == 0 and not args.no_extras:
         extras = extra_lines(torch, _native, dev, stream, key_bytes)
 
     if rank == 0:

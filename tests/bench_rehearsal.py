@@ -24,7 +24,7 @@ def main():
     out_path = sys.argv[1]
     world = int(os.environ["WORLD_SIZE"])
     rank = int(os.environ["RANK"])
-    sys.argv = ["bench.py", "--gpus", str(world), "--dist-backend", "gloo",
+    sys.argv = ["bench.py", "--full", "--gpus", str(world), "--dist-backend", "gloo",
                 "--tuples-per-gpu", "4096", "--steps", "10", "--warmup", "2",
                 "--configs3-tuples", str(1 << 16), "--configs3-steps", "4",
                 "--no-cpu-baseline", "--no-extras"]

@@ -111,6 +111,45 @@ def test_bench_digest_is_pinned_to_the_oracle(oracle_lib, example_key):
     assert bench.verify_outputs(torch, gold, ht, qt, 5, B)["ok"] is None
 
 
+def test_plain_run_is_the_default(monkeypatch):
+    """`--full` (the CPU baseline, verification, secondary blocks) and `--dump-outputs` are
+    off unless asked for."""
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse_args()
+    assert args.full is False and args.dump_outputs is None and args.steps == 7
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    args = bench.parse_args()
+    assert args.full is True and args.dump_outputs == "d"
+
+
+@pytest.mark.parametrize("n", [1000, bench.DUMP_SAMPLE, bench.DUMP_SAMPLE + 12345])
+def test_dump_outputs_exact_and_seeded(tmp_path, n):
+    """--dump-outputs: float64 / float32 arrays that hold the u64 counts, u32 hashes (high bit
+    set included) and u8 / u16 queues exactly; past DUMP_SAMPLE tuples the fixed, seeded,
+    ascending sample of tuple indices -- the same in every run."""
+    rng = np.random.default_rng(n)
+    h = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+    h[-1] = 0xFFFFFFFF
+    c = np.array([3, (1 << 40) + 1, 0], dtype=np.uint64)
+    idx = (np.arange(n) if n <= bench.DUMP_SAMPLE else
+           np.sort(np.random.default_rng(bench.SEED).integers(0, n, bench.DUMP_SAMPLE)))
+    assert len(idx) == min(n, bench.DUMP_SAMPLE) and (np.diff(idx) >= 0).all()
+    for qmax, qdt, view in ((24, np.uint8, np.uint8), (60000, np.uint16, np.int16)):
+        q = rng.integers(0, qmax, n, dtype=np.uint64).astype(qdt)
+        q[0] = qmax - 1
+        out = tmp_path / ("q%d" % qmax)
+        bench.dump_outputs(torch, str(out), torch.from_numpy(h.view(np.int32)),
+                           torch.from_numpy(q.view(view)), torch.from_numpy(c.view(np.int64)))
+        got = {p.name: np.load(p) for p in out.iterdir()}
+        assert sorted(got) == ["counts.npy", "hash_result.npy", "queue_number.npy"]
+        assert got["counts.npy"].dtype == got["hash_result.npy"].dtype == np.float64
+        assert got["queue_number.npy"].dtype == np.float32
+        np.testing.assert_array_equal(got["counts.npy"], c.astype(np.float64))
+        np.testing.assert_array_equal(got["hash_result.npy"].astype(np.uint32), h[idx])
+        np.testing.assert_array_equal(got["queue_number.npy"].astype(qdt), q[idx])
+        assert sum(a.nbytes for a in got.values()) <= 64 << 20
+
+
 def check_bench_line(line):
     """The fields VERDICT r02 asked every bench line to carry (configs[3] block, per-rank
     timings and placement, the verification of the timed work) are present and coherent."""

@@ -125,7 +125,7 @@ def test_nccl_world1_allreduce_counts_equal_oracle(tmp_path, oracle_lib, example
 def test_bench_under_torchrun_nproc1_reports_baseline_and_roofline(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "3", "--warmup", "1",
            "--tuples-per-gpu", str(1 << 22), "--no-extras", "--cpu-sample", "400",
            "--cpu-procs", "2"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")

@@ -13,5 +13,5 @@ for p in 1 2; do
     timeout -k 10 120 python tools/ws_order_ab.py 6 > $OUT/ab_$p.json 2> $OUT/ab_$p.err
 done
 echo "ab ok"
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
 echo "bench ok"

@@ -14,7 +14,7 @@ timeout -k 10 900 python -u -m pytest -q -m gpu --timeout 300 --timeout-method t
 tail -2 $O/pytest_gpu.log
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 tail -1 $O/smoke.log
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
 head -c 400 $O/bench.json; echo
 export TMPDIR=/tmp
 cd /tmp

@@ -8,11 +8,11 @@ OUT=$R/gpurun_out/${1:-dist_lines}
 mkdir -p $OUT
 cd $R
 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
-    --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --steps 20 --warmup 5 \
+    --master-addr 127.0.0.1 --master-port 29611 bench.py --full --gpus 1 --steps 20 --warmup 5 \
     > $OUT/torchrun_w1_rccl.json 2> $OUT/w1.err
 echo "w1 ok"
 RSS_BENCH_DEVICE=0 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 \
-    --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29612 bench.py --gpus 8 \
+    --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29612 bench.py --full --gpus 8 \
     --dist-backend gloo --tuples-per-gpu 67108864 --placement-probe 2 --steps 5 --warmup 2 \
     --settle-ms 0 --no-extras > $OUT/w8_gloo_rehearsal_1gpu.json 2> $OUT/w8.err
 echo "w8 ok"

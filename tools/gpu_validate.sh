@@ -24,7 +24,7 @@ if [ "$STAGE" = tests ] || [ "$STAGE" = all ]; then
 fi
 if [ "$STAGE" = perf ] || [ "$STAGE" = all ]; then
   set -e
-  timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+  timeout -k 10 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
   export TMPDIR=/tmp
   cd /tmp
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- \
