@@ -211,6 +211,34 @@ int rss_key_search_device(const uint32_t* d_windows, size_t nkeys,
                           uint32_t nqueues, uint64_t* d_counts, void* stream);
 
 /*
+ * A key's single-bit-flip neighbourhood (key search's local step; keysearch.refine climbs
+ * on it): the per-queue counts of the same n device-resident tuples under each of the
+ * RSS_KEY_NEIGHBOURS keys that differ from `key` in one bit.  Neighbour j has key bit j
+ * flipped (bit 0 = MSB of byte 0: byte j >> 3, mask 0x80 >> (j & 7)); these 128 bits are the
+ * ones of bytes 0..15, all that an IPv4 hash reads.  Toeplitz is linear in the key, so the
+ * neighbour's hash is the key's own hash XOR 32 consecutive bits of the tuple -- no table per
+ * neighbour: one launch hashes every tuple once per group of up to 32 neighbours and derives
+ * the group's queues with a funnel shift and a XOR each.  Key bit 127 feeds no hash, so row
+ * 127 holds the counts of `key` itself.
+ * d_counts: RSS_KEY_NEIGHBOURS x nqueues uint64, row j = neighbour j, overwritten (cleared by
+ * a kernel of the same call, then counted: the call can be captured into a graph); queue =
+ * hash % htable % nqueues and columns [min(htable, nqueues), nqueues) are zero, as for
+ * rss_key_search_device.  Exact for any htable, nqueues >= 1: up to 1259 queues are counted in
+ * lane-private LDS bins (32 neighbours per workgroup up to 39 queues, 16 up to 78, ...), up
+ * to 40288 in shared LDS bins, more by global atomics.  Any tuple alignment works; 16-byte
+ * aligned tuples take the 4-tuples-per-lane path.  n == 0 only clears the counts.
+ * RSS_EINVAL, before any device work, with rss_last_error naming the cause: key or counts
+ * NULL; n > 0 with tuples NULL; htable or nqueues 0; key->len < 16 (a shorter key wraps in
+ * its windows and a flipped bit is no longer one 32-bit delta); a key whose window[] is not
+ * that of its own bytes[], i.e. one that rss_key_select_fields changed.  Field-selected keys
+ * and IPv6 keys are out of scope.
+ */
+#define RSS_KEY_NEIGHBOURS 128
+int rss_key_neighbourhood_device(const rss_key* key, const rss_tuple4* d_tuples, size_t n,
+                                 uint32_t htable, uint32_t nqueues, uint64_t* d_counts,
+                                 void* stream);
+
+/*
  * IPv6.  36-byte input = src addr (16 B) | dst addr (16 B) |
  * src port | dst port, the layout of the Microsoft RSS IPv6 hash; stored as nine
  * host-order words whose big-endian bytes are that input (w[0..3] src, w[4..7]
@@ -406,6 +434,13 @@ int rss_csv6_hash_file(rss_ctx* ctx, const rss_key6* key, const char* in_path,
 int rss_key_search_host(rss_ctx* ctx, const rss_key* keys, size_t nkeys,
                         const rss_tuple4* h_tuples, size_t n, uint32_t htable,
                         uint32_t nqueues, uint64_t* h_counts);
+
+/* rss_key_neighbourhood_device on host buffers (h_counts: RSS_KEY_NEIGHBOURS x nqueues
+ * uint64), as rss_key_search_host: takes the context's lock, uploads the tuples, launches,
+ * copies the counts back.  Synchronous.  The same validation (and a NULL ctx) is refused
+ * first; n == 0 zeroes h_counts on the host. */
+int rss_key_neighbourhood_host(rss_ctx* ctx, const rss_key* key, const rss_tuple4* h_tuples,
+                               size_t n, uint32_t htable, uint32_t nqueues, uint64_t* h_counts);
 
 /* rss_hash6_device on host buffers: rss_hash_host's contract and path (the same staging,
  * small-batch path, pipeline and direct DMA of page-locked buffers), 36-byte tuples. */

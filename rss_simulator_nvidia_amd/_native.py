@@ -39,8 +39,10 @@ EXPORTED_SYMBOLS = (
     "rss_pcap_parse6", "rss_hash6_device_reta", "rss_hash6_host_reta", "rss_csv_parse6",
     "rss_csv_format6_bound", "rss_csv_format6", "rss_csv6_hash_text", "rss_csv6_hash_file",
     "rss_counts_workspace_bytes", "rss_hash_device_ws", "rss_hash6_device_ws",
-    "rss_parse_dotted", "rss_parse_ipv6",
+    "rss_parse_dotted", "rss_parse_ipv6", "rss_key_neighbourhood_device",
+    "rss_key_neighbourhood_host",
 )
+KEY_NEIGHBOURS = 128  # RSS_KEY_NEIGHBOURS: the key bits an IPv4 hash reads
 FIELD_SRC_IP, FIELD_DST_IP, FIELD_SRC_PORT, FIELD_DST_PORT = 1, 2, 4, 8
 FIELDS_IP, FIELDS_ALL = 3, 15
 ENOTSUP = -95
@@ -103,6 +105,8 @@ def _bind(lib):
                            ctypes.c_int], ctypes.c_int),
         "rss_csv_format_bound": ([sz, u32], sz),
         "rss_key_search_device": ([vp, sz, vp, sz, u32, u32, vp, vp], ctypes.c_int),
+        "rss_key_neighbourhood_device": ([key_p, vp, sz, u32, u32, vp, vp], ctypes.c_int),
+        "rss_key_neighbourhood_host": ([vp, key_p, vp, sz, u32, u32, vp], ctypes.c_int),
         "rss_key_select_fields": ([key_p, u32], ctypes.c_int),
         "rss_hash_device_reta": ([key_p, vp, sz, u32, vp, u32, vp, vp, vp, u32, vp], ctypes.c_int),
         "rss_hash_host_reta": ([vp, key_p, vp, sz, u32, vp, u32, vp, vp, vp, u32], ctypes.c_int),
@@ -509,6 +513,20 @@ class HostContext:
                "rss_key_search_host")
         return out
 
+    def key_neighbourhood(self, key, tuples, htable, nqueues):
+        """Per-queue counts (uint64[128, min(htable, nqueues)]) of ``tuples`` under each
+        single-bit flip of the prepared ``key`` (``rss_key_neighbourhood_host``): row j has
+        key bit j flipped (0 = MSB of byte 0), row 127 is the key's own counts."""
+        htable, nqueues = queue_modulus(htable, nqueues)
+        arr = np.ascontiguousarray(tuples)
+        if arr.dtype != TUPLE_DTYPE:
+            arr = np.ascontiguousarray(arr, dtype=np.uint32).reshape(-1, 3)
+        out = np.zeros((KEY_NEIGHBOURS, nqueues), dtype=np.uint64)
+        _check(self._lib.rss_key_neighbourhood_host(self._ctx, ctypes.byref(key), arr.ctypes.data,
+                                                    len(arr), htable, nqueues, out.ctypes.data),
+               "rss_key_neighbourhood_host")
+        return out
+
 
 _default_ctx = None
 _ctx_lock = threading.Lock()
@@ -674,6 +692,14 @@ def key_search_device(windows_ptr, nkeys, tuples_ptr, n, htable, nqueues, counts
     htable, nqueues = queue_modulus(htable, nqueues)
     _check(load().rss_key_search_device(windows_ptr, nkeys, tuples_ptr, n, htable, nqueues,
                                         counts_ptr, stream), "rss_key_search_device")
+
+
+def key_neighbourhood_device(key, tuples_ptr, n, htable, nqueues, counts_ptr, stream=None):
+    """Stream-ordered ``rss_key_neighbourhood_device`` on raw device pointers (ints);
+    ``counts_ptr`` holds ``128 x queue_modulus(htable, nqueues)[1]`` uint64."""
+    htable, nqueues = queue_modulus(htable, nqueues)
+    _check(load().rss_key_neighbourhood_device(ctypes.byref(key), tuples_ptr, n, htable, nqueues,
+                                               counts_ptr, stream), "rss_key_neighbourhood_device")
 
 
 def generate_device(seed, first_index, n, tuples_ptr, stream=None):

@@ -67,6 +67,27 @@ void rotation_windows(const uint8_t* key, size_t len, uint32_t* window, int nbit
     }
 }
 
+// rss_key_neighbourhood_device / _host: everything that can be refused before device work
+int check_neighbourhood(const char* who, const rss_key* key, const rss_tuple4* tuples, size_t n,
+                        uint32_t htable, uint32_t nqueues, const uint64_t* counts) {
+    if (!key || !counts) return rss_set_error(RSS_EINVAL, "%s: key or counts is NULL", who);
+    if (n && !tuples) return rss_set_error(RSS_EINVAL, "%s: tuples is NULL", who);
+    if (htable < 1 || nqueues < 1)
+        return rss_set_error(RSS_EINVAL, "%s: htable (%u) and nqueues (%u) must be >= 1", who,
+                             htable, nqueues);
+    if (key->len < 16)
+        return rss_set_error(RSS_EINVAL,
+                             "%s: key of %u bytes: keys shorter than 16 bytes wrap, their "
+                             "neighbours are not single-word deltas", who, key->len);
+    uint32_t own[RSS_INPUT_BITS];
+    rotation_windows(key->bytes, std::min<size_t>(key->len, RSS_KEY_MAX_BYTES), own, RSS_INPUT_BITS);
+    if (memcmp(own, key->window, sizeof own) != 0)
+        return rss_set_error(RSS_EINVAL,
+                             "%s: the key's windows are not those of its bytes (field-selected "
+                             "keys are not supported)", who);
+    return RSS_OK;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------ C ABI ---------
@@ -214,6 +235,16 @@ int rss_key_search_device(const uint32_t* d_windows, size_t nkeys, const rss_tup
                           void* stream) {
     return rss::launch_search(d_windows, nkeys, d_tuples, n, htable, nqueues, d_counts,
                               static_cast<hipStream_t>(stream));
+}
+
+int rss_key_neighbourhood_device(const rss_key* key, const rss_tuple4* d_tuples, size_t n,
+                                 uint32_t htable, uint32_t nqueues, uint64_t* d_counts,
+                                 void* stream) {
+    int rc = check_neighbourhood("rss_key_neighbourhood_device", key, d_tuples, n, htable, nqueues,
+                                 d_counts);
+    if (rc) return rc;
+    return rss::launch_neighbourhood(key, d_tuples, n, htable, nqueues, d_counts,
+                                     static_cast<hipStream_t>(stream));
 }
 
 int rss_generate_tuples(uint64_t seed, uint64_t first_index, size_t n, rss_tuple4* d_tuples,
@@ -669,6 +700,46 @@ int rss_key_search_host(rss_ctx* ctx, const rss_key* keys, size_t nkeys,
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess)
             rc = rss_set_error(RSS_EIO, "rss_key_search_host: %s", hipGetErrorString(e));
+    }
+    cleanup();
+    return rc;
+}
+
+int rss_key_neighbourhood_host(rss_ctx* ctx, const rss_key* key, const rss_tuple4* h_tuples,
+                               size_t n, uint32_t htable, uint32_t nqueues, uint64_t* h_counts) {
+    const char* who = "rss_key_neighbourhood_host";
+    int rc = check_neighbourhood(who, key, h_tuples, n, htable, nqueues, h_counts);
+    if (rc) return rc;
+    if (!ctx) return rss_set_error(RSS_EINVAL, "%s: context is NULL", who);
+    const size_t count_bytes = sizeof(uint64_t) * RSS_KEY_NEIGHBOURS * nqueues;
+    if (n == 0) {
+        memset(h_counts, 0, count_bytes);
+        return RSS_OK;
+    }
+    std::lock_guard<std::mutex> lock(ctx->mu);  // (struct rss_ctx)
+    RSS_HIP_CHECK(hipSetDevice(ctx->device));
+    rss_tuple4* d_t = nullptr;
+    uint64_t* d_c = nullptr;
+    hipStream_t s = ctx->stream[0];
+    auto cleanup = [&] {
+        (void)hipStreamSynchronize(s);
+        (void)hipFree(d_t);
+        (void)hipFree(d_c);
+    };
+    hipError_t e = hipMalloc(&d_t, n * sizeof(rss_tuple4));
+    if (e == hipSuccess) e = hipMalloc(&d_c, count_bytes);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d_t, h_tuples, n * sizeof(rss_tuple4), hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) {
+        cleanup();
+        return rss_set_error(e == hipErrorOutOfMemory ? RSS_ENOMEM : RSS_EIO, "%s: %s", who,
+                             hipGetErrorString(e));
+    }
+    rc = rss::launch_neighbourhood(key, d_t, n, htable, nqueues, d_c, s);
+    if (rc == RSS_OK) {
+        e = hipMemcpyAsync(h_counts, d_c, count_bytes, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) rc = rss_set_error(RSS_EIO, "%s: %s", who, hipGetErrorString(e));
     }
     cleanup();
     return rc;

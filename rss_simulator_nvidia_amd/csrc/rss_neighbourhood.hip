@@ -1,0 +1,252 @@
+// rss_neighbourhood.hip -- a key's single-bit-flip neighbourhood (key search's local step): the
+// per-queue counts of the same device-resident tuples under each of the 128 keys that differ
+// from one key in one of the bits that feed an IPv4 hash, in one launch.  No test hooks:
+// compiled once for both libraries.
+//
+// Toeplitz is linear in the key as well as in the input: window i is key bits [i, i + 32), so
+// key bit j sits at bit i + 31 - j of window i and flipping it toggles hash bit b exactly when
+// input bit b + j - 31 is set.  With X the 96-bit integer whose bit i is input bit i (0 = MSB of
+// the source ip; words brev(sip), brev(dip), brev(ports) from the low end) and R = X << 31,
+//     hash(key ^ bit j, x) = hash(key, x) ^ ((R >> j) & 0xFFFFFFFF),   j = 0 .. 127
+// for a key of >= 16 bytes (no wrap in the windows).  R has 127 bits, so j = 127 changes nothing:
+// row 127 is the key itself.  A neighbour therefore costs no table of its own -- one base hash
+// per tuple on the conflict-free small tables (21 ds_read_b32, 2688 B of LDS), then per
+// neighbour one v_alignbit_b32, one XOR, the bucket / queue step and one LDS add.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstring>
+#include <algorithm>
+
+#include "rss_engine.h"
+#include "rss_kernel_common.h"
+
+namespace {
+
+// Work split.  A workgroup (blockIdx.y) serves `ng` consecutive neighbours j0 = ng * y .. and
+// histograms its grid-stride share (blockIdx.x) of the tuples for all of them; ng is a power
+// of two <= 32, so the group's deltas all come from ONE pair of R's words (j0 >> 5, uniform)
+// shifted by (j0 & 31) + k: the pair is picked and pre-shifted once per tuple and k is a
+// constant of the unrolled loop.
+// Bins.  u32, [queue][neighbour][lane column] (kBinCols = 32 columns, one per bank, as the
+// packed search kernel's): a half-wave's adds never collide, the neighbour's 128-byte offset is
+// the ds_add's immediate and the queue's row a multiple of a compile-time size --
+// [neighbour][queue][column] would want a base register per neighbour instead.  At H = 128,
+// Q = 24 a neighbour is 6 full-rate VALU instructions and one ds_add_u32.  ng is the largest
+// power of two whose bins fit beside the tables:
+//     ng (private bins)   32    16    8     4     2     1
+//     queues up to        39    78    157   314   629   1259
+// Past 1259 queues the bins lose their columns ([queue][neighbour], ng = 16 up to 2518 queues,
+// 8 to 5036, 4 to 10072, 2 to 20144, 1 to 40288), and past those every (tuple, neighbour) is
+// one global atomic: exact for any H, Q, only slower.  These two run one kernel body with ng
+// at run time (kNG = 0).
+constexpr uint32_t kNbrBinBytesMax = kLdsBytes - kSmallLutBytes;  // 161152
+
+inline uint32_t neighbours_per_workgroup(uint64_t bytes_per_neighbour) {
+    uint32_t ng = 32;
+    while (ng > 1 && bytes_per_neighbour * ng > kNbrBinBytesMax) ng >>= 1;
+    return ng;
+}
+
+__device__ __forceinline__ uint32_t alignbit(uint32_t hi, uint32_t lo, uint32_t s) {
+    return __builtin_amdgcn_alignbit(hi, lo, s);  // low word of {hi, lo} >> (s & 31)
+}
+
+// bits [32 word + s0, 32 word + s0 + 64) of R for one tuple: neighbour j0 + k's delta is the
+// low word of this span >> k  (s0 + k <= 31)
+__device__ __forceinline__ uint2 flip_span(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t word,
+                                           uint32_t s0) {
+    const uint32_t x0 = __brev(w0), x1 = __brev(w1), x2 = __brev(w2);
+    // R = X << 31 as words r0 .. r3 (r4 = 0)
+    const uint32_t r0 = x0 << 31, r1 = alignbit(x1, x0, 1), r2 = alignbit(x2, x1, 1), r3 = x2 >> 1;
+    uint32_t lo, hi;
+    switch (word) {  // uniform
+        case 0: lo = r0; hi = r1; break;
+        case 1: lo = r1; hi = r2; break;
+        case 2: lo = r2; hi = r3; break;
+        default: lo = r3; hi = 0u; break;
+    }
+    return make_uint2(alignbit(hi, lo, s0), hi >> s0);
+}
+
+template <int kNG, bool kHPow2, int kQMode, int kHist>
+__global__ __launch_bounds__(kBlock) void rss_key_neighbourhood_kernel(const LaunchParams p) {
+    __shared__ uint32_t lut[kSmallLutDwords];
+    extern __shared__ uint32_t bins[];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t ng = kNG ? (uint32_t)kNG : p.nkeys;
+    const uint32_t j0 = ng * blockIdx.y;
+    const uint32_t word = j0 >> 5, s0 = j0 & 31u;
+    build_small_lut(lut, p.window, tid);
+    const uint32_t nbins =
+        kHist == HIST_PRIVATE ? p.Q * ng * kBinCols : (kHist == HIST_SHARED ? p.Q * ng : 0u);
+    for (uint32_t e = tid; e < nbins; e += kBlock) bins[e] = 0;
+    __syncthreads();
+
+    char* bins_colb = reinterpret_cast<char*>(bins + (tid & (kBinCols - 1)));
+    constexpr uint32_t kRowBytes = kNG * kBinCols * 4;  // private bins: one queue's row
+    // QM_FAST8 (H <= 256) folded into the row's byte offset as in the packed search kernel:
+    // q * row = b * row - d * (Q * row), d = floor(b / Q) -- two full-rate 24-bit multiplies,
+    // the second a v_mad_i32_i24, where queue_of's b - d * Q compiles to a quarter-rate
+    // v_mul_lo_u32 (Q * row <= 161152 and b * row < 2^20 fit 24 bits)
+    const int neg_q_row = -(int)(p.Q * kRowBytes);
+    unsigned long long* rows = p.counts + (size_t)j0 * p.q_stride;  // row k at k * q_stride
+    auto count = [&](uint32_t w0, uint32_t w1, uint32_t w2) {
+        const uint32_t h = toeplitz_hash_small(lut, w0, w1, w2);
+        const uint2 span = flip_span(w0, w1, w2, word, s0);
+        auto neighbour = [&](uint32_t k) {
+            const uint32_t b = bucket_of<kHPow2>(h ^ alignbit(span.y, span.x, k), p);
+            if constexpr (kHist == HIST_PRIVATE) {
+                uint32_t row;
+                if constexpr (kQMode == QM_FAST8) {
+                    const uint32_t d = __umul24(b, p.q_m16) >> 16;
+                    row = (uint32_t)__mul24((int)d, neg_q_row) + b * kRowBytes;
+                } else {
+                    row = queue_of<kQMode>(b, p) * kRowBytes;
+                }
+                __hip_atomic_fetch_add(reinterpret_cast<uint32_t*>(bins_colb + row) + k * kBinCols,
+                                       1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            } else if constexpr (kHist == HIST_SHARED) {
+                __hip_atomic_fetch_add(&bins[queue_of<kQMode>(b, p) * ng + k], 1u, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_WORKGROUP);
+            } else {
+                atomicAdd(&rows[(size_t)k * p.q_stride + queue_of<kQMode>(b, p)], 1ull);
+            }
+        };
+        if constexpr (kNG != 0) {
+#pragma unroll
+            for (uint32_t k = 0; k < (uint32_t)kNG; ++k) neighbour(k);
+        } else {
+            for (uint32_t k = 0; k < ng; ++k) neighbour(k);
+        }
+    };
+    const uint64_t gtid = (uint64_t)blockIdx.x * kBlock + tid;
+    const uint64_t gstride = (uint64_t)gridDim.x * kBlock;
+    uint64_t tail_begin = 0;
+    if (((uintptr_t)p.tuples & 15u) == 0) {  // 16-byte aligned: four tuples per lane
+        const uint4* __restrict__ src = reinterpret_cast<const uint4*>(p.tuples);
+        const uint64_t ngroups = p.n >> 2;
+        for (uint64_t g = gtid; g < ngroups; g += gstride) {
+            const uint4 a = src[3 * g + 0];
+            const uint4 b = src[3 * g + 1];
+            const uint4 c = src[3 * g + 2];
+            count(a.x, a.y, a.z);
+            count(a.w, b.x, b.y);
+            count(b.z, b.w, c.x);
+            count(c.y, c.z, c.w);
+        }
+        tail_begin = ngroups << 2;
+    }
+    for (uint64_t i = tail_begin + gtid; i < p.n; i += gstride) {
+        const uint32_t* t = reinterpret_cast<const uint32_t*>(p.tuples) + 3 * i;
+        count(t[0], t[1], t[2]);
+    }
+    if constexpr (kHist != HIST_GLOBAL) {
+        __syncthreads();
+        const uint32_t ng_shift = 31 - __clz(ng);
+        for (uint32_t e = tid; e < p.Q * ng; e += kBlock) {  // e = q * ng + k
+            uint32_t s;
+            if constexpr (kHist == HIST_PRIVATE) {
+                s = 0;
+                for (uint32_t c = 0; c < kBinCols; ++c)
+                    s += bins[e * kBinCols + ((c + e) & (kBinCols - 1))];
+            } else {
+                s = bins[e];
+            }
+            if (s)
+                atomicAdd(&rows[(size_t)(e & (ng - 1)) * p.q_stride + (e >> ng_shift)],
+                          (unsigned long long)s);
+        }
+    }
+}
+
+// the counts are overwritten: cleared by a kernel, so that the entry point can be captured
+// into a graph like any other launch
+__global__ __launch_bounds__(kBlock) void rss_zero_counts_kernel(unsigned long long* counts,
+                                                                 uint64_t n) {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) counts[i] = 0;
+}
+
+template <int kNG, bool kHPow2, int kHist>
+KernelFn pick_nbr_qmode(int qmode) {
+    switch (qmode) {
+        case QM_MASK: return rss_key_neighbourhood_kernel<kNG, kHPow2, QM_MASK, kHist>;
+        case QM_FAST8: return rss_key_neighbourhood_kernel<kNG, kHPow2, QM_FAST8, kHist>;
+        case QM_FAST16: return rss_key_neighbourhood_kernel<kNG, kHPow2, QM_FAST16, kHist>;
+        default: return rss_key_neighbourhood_kernel<kNG, kHPow2, QM_FAST32, kHist>;
+    }
+}
+
+template <int kNG, int kHist>
+KernelFn pick_nbr_modes(bool h_pow2, int qmode) {
+    return h_pow2 ? pick_nbr_qmode<kNG, true, kHist>(qmode) : pick_nbr_qmode<kNG, false, kHist>(qmode);
+}
+
+KernelFn pick_nbr(int hist, uint32_t ng, bool h_pow2, int qmode) {
+    if (hist == HIST_SHARED) return pick_nbr_modes<0, HIST_SHARED>(h_pow2, qmode);
+    if (hist != HIST_PRIVATE) return pick_nbr_modes<0, HIST_GLOBAL>(h_pow2, qmode);
+    switch (ng) {
+        case 32: return pick_nbr_modes<32, HIST_PRIVATE>(h_pow2, qmode);
+        case 16: return pick_nbr_modes<16, HIST_PRIVATE>(h_pow2, qmode);
+        case 8: return pick_nbr_modes<8, HIST_PRIVATE>(h_pow2, qmode);
+        case 4: return pick_nbr_modes<4, HIST_PRIVATE>(h_pow2, qmode);
+        case 2: return pick_nbr_modes<2, HIST_PRIVATE>(h_pow2, qmode);
+        default: return pick_nbr_modes<1, HIST_PRIVATE>(h_pow2, qmode);
+    }
+}
+
+// Workgroups along x.  A workgroup's fixed cost is its bins: q * ng * 32 dwords cleared and
+// summed again by 1024 lanes, q * ng / 16 LDS accesses per lane, against ng adds per tuple --
+// so q / 2 tuples per lane (at least 16: four 4-tuple loads) keep it near a tenth of the work.
+// That is far less than the search kernels' 256K tuples per workgroup (their 120 KiB table
+// build), and 2^20 tuples already fill the device: 64 x 4 workgroups at Q = 24.  No more than
+// one round of workgroups (cu_count / y), since each may hold a CU's whole LDS.
+inline unsigned neighbourhood_grid_x(size_t n, uint32_t q_eff, unsigned gy, int cu_count) {
+    const uint64_t per_wg = (uint64_t)kBlock * std::max<uint32_t>(16u, q_eff / 2);
+    const uint64_t slices = (n + per_wg - 1) / per_wg;
+    const uint64_t cap = std::max<uint64_t>(1, (uint64_t)cu_count / gy);
+    return (unsigned)std::min(slices, cap);
+}
+
+}  // namespace
+
+// ------------------------------------------------------ launcher (rss_engine.h) --
+namespace rss {
+
+int launch_neighbourhood(const rss_key* key, const rss_tuple4* d_tuples, size_t n, uint32_t htable,
+                         uint32_t nqueues, uint64_t* d_counts, hipStream_t stream) {
+    DeviceInfo info;
+    int rc = device_info(&info);
+    if (rc) return rc;
+    const uint64_t cells = (uint64_t)RSS_KEY_NEIGHBOURS * nqueues;
+    const unsigned zero_grid =
+        (unsigned)std::min<uint64_t>((cells + kBlock - 1) / kBlock, 4u * (unsigned)info.cu_count);
+    hipLaunchKernelGGL(rss_zero_counts_kernel, dim3(zero_grid), dim3(kBlock), 0, stream,
+                       reinterpret_cast<unsigned long long*>(d_counts), cells);
+    RSS_HIP_CHECK(hipGetLastError());
+    if (n == 0) return RSS_OK;
+    LaunchParams p;
+    memset(&p, 0, sizeof p);
+    memcpy(p.window, key->window, sizeof p.window);
+    p.tuples = d_tuples;
+    p.n = n;
+    p.counts = reinterpret_cast<unsigned long long*>(d_counts);
+    p.q_stride = nqueues;  // rows keep the caller's nqueues; queues >= min(H, Q) stay zero
+    const uint32_t q_eff = effective_queues(htable, nqueues, nullptr);
+    int qmode, hist;
+    uint32_t bin_bytes;  // of one neighbour
+    const bool h_pow2 = setup_modes(&p, htable, q_eff, true, &qmode, &hist, &bin_bytes,
+                                    kNbrBinBytesMax);
+    const uint32_t ng = hist == HIST_GLOBAL ? 32u : neighbours_per_workgroup(bin_bytes);
+    p.nkeys = ng;
+    const unsigned gy = RSS_KEY_NEIGHBOURS / ng;
+    const unsigned gx = neighbourhood_grid_x(n, hist == HIST_PRIVATE ? q_eff : q_eff / kBinCols, gy,
+                                             info.cu_count);
+    hipLaunchKernelGGL(pick_nbr(hist, ng, h_pow2, qmode), dim3(gx, gy), dim3(kBlock),
+                       bin_bytes * ng, stream, p);
+    RSS_HIP_CHECK(hipGetLastError());
+    return RSS_OK;
+}
+
+}  // namespace rss

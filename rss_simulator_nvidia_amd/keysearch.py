@@ -10,6 +10,11 @@ of the H buckets, so a perfect key gives it ``n * slots(q) / H`` flows.
 
     python -m rss_simulator_nvidia_amd.keysearch --ips-file flows.csv \\
         --htable-size 128 --num-queues 24 --keys 4096 --top 5 --out best_key.txt
+
+``--refine STEPS`` then improves the best candidate (and a ``--key-file`` key) by local
+search: Toeplitz is linear in the key, so all 128 single-bit flips of a key are scored in
+one launch from the key's own hashes (``rss_key_neighbourhood_device``), and :func:`refine`
+flips the best bit until none improves the spread.
 """
 import argparse
 import random
@@ -85,6 +90,71 @@ def search(tuples, htable, nqueues, n_keys=1024, seed=0, top=10, extra_keys=()):
              "used": int(m["used"][i]), "counts": counts[i]} for i in order[:top]]
 
 
+def flip_bit(key, j):
+    """``key`` with bit ``j`` flipped (0 = MSB of byte 0), as a new list."""
+    out = [int(b) for b in key]
+    out[j >> 3] ^= 0x80 >> (j & 7)
+    return out
+
+
+def neighbourhood(key, tuples, htable, nqueues, ctx=None):
+    """uint64 counts ``[128, min(H, Q)]`` of packed ``tuples`` under every single-bit flip of
+    ``key`` (GPU, one launch): row j = ``flip_bit(key, j)``; key bit 127 feeds no IPv4 hash,
+    so row 127 is ``key`` itself."""
+    ctx = ctx or _native.default_context()
+    return ctx.key_neighbourhood(_native.prepare_key(key), tuples, htable, nqueues)
+
+
+def _resident_neighbourhood(tuples, htable, nqueues):
+    """``key -> counts[128, min(H, Q)]`` on tuples uploaded once: one
+    ``rss_key_neighbourhood_device`` launch per call."""
+    import torch
+    arr = np.ascontiguousarray(tuples)
+    if arr.dtype != _native.TUPLE_DTYPE:
+        arr = np.ascontiguousarray(arr, dtype=np.uint32).reshape(-1, 3)
+    n = len(arr)
+    dev = torch.device("cuda:%d" % _native.default_context().device)
+    flat = np.ascontiguousarray(arr).view(np.int32).reshape(-1)
+    d_tuples = torch.from_numpy(flat).to(dev)
+    width = _native.queue_modulus(htable, nqueues)[1]
+    d_counts = torch.empty((_native.KEY_NEIGHBOURS, width), dtype=torch.int64, device=dev)
+
+    def score(key):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _native.key_neighbourhood_device(_native.prepare_key(key), d_tuples.data_ptr(), n, htable,
+                                         nqueues, d_counts.data_ptr(), stream)
+        return d_counts.cpu().numpy().view(np.uint64)
+
+    return score
+
+
+def refine(key, tuples, htable, nqueues, max_steps=64, neighbourhood=None):
+    """Hill-climb ``key`` over single-bit flips (steepest descent on ``(max_load, chi2)``).
+
+    Each step scores the key's 128 neighbours (one ``rss_key_neighbourhood_device`` launch
+    on tuples uploaded once; or ``neighbourhood(key) -> counts[128, Q]`` when given) with
+    :func:`balance` and flips the bit whose row has the lexicographically smallest
+    ``(max_load, chi2)``, as long as that is strictly below the key's own (row 127); it stops
+    at a local optimum or after ``max_steps`` flips.  Returns a dict: ``key``, ``max_load``,
+    ``chi2``, ``used``, ``counts`` (of the returned key) and ``flips`` (the bits, in order).
+    """
+    key = [int(b) for b in key]
+    score = neighbourhood or _resident_neighbourhood(tuples, htable, nqueues)
+    flips = []
+    own = _native.KEY_NEIGHBOURS - 1
+    counts = np.asarray(score(key))
+    while True:
+        m = balance(counts, htable, nqueues)
+        best = int(np.lexsort((m["chi2"], m["max_load"]))[0])
+        better = (m["max_load"][best], m["chi2"][best]) < (m["max_load"][own], m["chi2"][own])
+        if not better or len(flips) >= max_steps:
+            return {"key": key, "max_load": float(m["max_load"][own]), "chi2": float(m["chi2"][own]),
+                    "used": int(m["used"][own]), "counts": counts[own].copy(), "flips": flips}
+        key = flip_bit(key, best)
+        flips.append(best)
+        counts = np.asarray(score(key))
+
+
 def load_tuples(ips_file):
     """Packed tuples of a 4-tuple CSV: native fast path, else the pandas ingest."""
     parsed = _native.csv_parse(np.fromfile(ips_file, dtype=np.uint8))
@@ -105,6 +175,9 @@ def main(argv=None):
     p.add_argument("--key-file", metavar="PATH", dest="key",
                    type=apt_decorator(HashKey.from_file),
                    help="also score this key (e.g. the one in use)")
+    p.add_argument("--refine", metavar="STEPS", type=int, default=0,
+                   help="then hill-climb the top-ranked key (and the --key-file key) over "
+                        "single-bit flips, at most STEPS flips each")
     p.add_argument("--out", metavar="PATH", help="write the best key in --key-file format")
     args = p.parse_args(argv)
     tuples = load_tuples(args.ips_file)
@@ -119,6 +192,16 @@ def main(argv=None):
     for r in ranked:
         print("%s  max_load %.4f chi2 %.2f queues used %d"
               % (key_text(r["key"]), r["max_load"], r["chi2"], r["used"]))
+    if args.refine > 0:
+        starts = [ranked[0]["key"]] + extra
+        score = _resident_neighbourhood(tuples, args.htable_size, args.num_queues)
+        refined = [refine(k, tuples, args.htable_size, args.num_queues, args.refine, score)
+                   for k in starts]
+        refined.sort(key=lambda r: (r["max_load"], r["chi2"]))
+        for r in refined:
+            print("%s  max_load %.4f chi2 %.2f queues used %d"
+                  % (key_text(r["key"]), r["max_load"], r["chi2"], r["used"]))
+        ranked = refined + ranked  # --out takes the best refined key
     if args.out:
         with open(args.out, "w") as f:
             f.write(key_text(ranked[0]["key"]))
