@@ -231,7 +231,7 @@ int rss_key_search_device(const uint32_t* d_windows, size_t nkeys,
  * NULL; n > 0 with tuples NULL; htable or nqueues 0; key->len < 16 (a shorter key wraps in
  * its windows and a flipped bit is no longer one 32-bit delta); a key whose window[] is not
  * that of its own bytes[], i.e. one that rss_key_select_fields changed.  Field-selected keys
- * and IPv6 keys are out of scope.
+ * are out of scope; IPv6 tuples: rss_key_neighbourhood6_device.
  */
 #define RSS_KEY_NEIGHBOURS 128
 int rss_key_neighbourhood_device(const rss_key* key, const rss_tuple4* d_tuples, size_t n,
@@ -271,6 +271,48 @@ int rss_hash6_device(const rss_key6* key, const rss_tuple6* d_tuples, size_t n,
 int rss_hash6_device_ws(const rss_key6* key, const rss_tuple6* d_tuples, size_t n,
                         uint32_t htable, uint32_t nqueues, uint32_t* d_hash, void* d_queue,
                         uint64_t* d_counts, uint32_t flags, uint64_t* d_workspace, void* stream);
+
+/*
+ * Key search over IPv6 tuples: rss_key_search_device's contract for 36-byte tuples and the
+ * 288 windows of an rss_key6.  d_windows: nkeys x RSS_INPUT6_BITS uint32 in device memory,
+ * key k's rss_key6::window at k*288 -- a field-selected key (rss_key6_select_fields) is just
+ * other windows, so it works.  d_counts: nkeys x nqueues uint64, row k = key k, overwritten
+ * (cleared by a kernel of the same call); queue = hash % htable % nqueues and columns
+ * [min(htable, nqueues), nqueues) are zero.  One launch per 65535 key groups: a workgroup
+ * builds 63 conflict-free tables of 8-byte entries shared by its 8 keys (power-of-two htable
+ * <= 256, up to 144 queues), 4 keys (power-of-two htable <= 65536, up to 288 queues) or 2 keys
+ * (any htable; lane-private LDS bins up to 577 queues, shared LDS bins up to 18464, global
+ * atomics beyond) and histograms its share of the tuples.  Exact for any htable, nqueues >= 1,
+ * any n (0 only clears) and any 4-byte aligned tuple pointer; 16-byte aligned tuples take the
+ * 4-tuples-per-lane path.  RSS_EINVAL, before any device work, with rss_last_error naming the
+ * entry and the cause: windows or counts NULL; nkeys == 0; n > 0 with tuples NULL; htable or
+ * nqueues 0.
+ */
+int rss_key_search6_device(const uint32_t* d_windows, size_t nkeys,
+                           const rss_tuple6* d_tuples, size_t n, uint32_t htable,
+                           uint32_t nqueues, uint64_t* d_counts, void* stream);
+
+/*
+ * A 40-byte key's single-bit-flip neighbourhood over IPv6 tuples, as
+ * rss_key_neighbourhood_device: the RSS_KEY6_NEIGHBOURS keys that differ from `key` in one of
+ * the 320 bits an IPv6 hash can read.  With X the 288-bit integer whose bit i is input bit i
+ * and R = X << 31 (319 bits), hash(key ^ bit j, x) = hash(key, x) ^ ((R >> j) & 0xFFFFFFFF);
+ * key bit 319 feeds no hash, so row 319 holds the counts of `key` itself.
+ * d_counts: RSS_KEY6_NEIGHBOURS x nqueues uint64, row j = neighbour j, overwritten (cleared by
+ * a kernel of the same call: capturable into a graph); columns [min(htable, nqueues), nqueues)
+ * are zero.  Exact for any htable, nqueues >= 1: up to 1217 queues in lane-private LDS bins (32
+ * neighbours per workgroup up to 38 queues, 16 up to 76, ...), up to 38944 in shared LDS bins,
+ * more by global atomics.  Any 4-byte tuple alignment; n == 0 only clears the counts.
+ * RSS_EINVAL, before any device work, with rss_last_error naming the entry and the cause: key
+ * or counts NULL; n > 0 with tuples NULL; htable or nqueues 0; key->len < 40 (a shorter key
+ * wraps inside its 288 windows and a flipped bit is no longer one 32-bit delta); a key whose
+ * windows are not a plain Toeplitz sequence (window[i + 1] >> 1 != window[i] & 0x7FFFFFFF for
+ * some i), which is how a key changed by rss_key6_select_fields shows.
+ */
+#define RSS_KEY6_NEIGHBOURS 320
+int rss_key_neighbourhood6_device(const rss_key6* key, const rss_tuple6* d_tuples, size_t n,
+                                  uint32_t htable, uint32_t nqueues, uint64_t* d_counts,
+                                  void* stream);
 
 /*
  * Host-memory convenience path (CSV in -> CSV out): owns device buffers.
@@ -441,6 +483,19 @@ int rss_key_search_host(rss_ctx* ctx, const rss_key* keys, size_t nkeys,
  * first; n == 0 zeroes h_counts on the host. */
 int rss_key_neighbourhood_host(rss_ctx* ctx, const rss_key* key, const rss_tuple4* h_tuples,
                                size_t n, uint32_t htable, uint32_t nqueues, uint64_t* h_counts);
+
+/* rss_key_search6_device on host buffers (keys: nkeys prepared rss_key6; h_counts: nkeys x
+ * nqueues uint64), as rss_key_search_host.  Synchronous.  Refuses what the device entry
+ * refuses (and a NULL ctx or keys, or a key that was not prepared) before any device work. */
+int rss_key_search6_host(rss_ctx* ctx, const rss_key6* keys, size_t nkeys,
+                         const rss_tuple6* h_tuples, size_t n, uint32_t htable,
+                         uint32_t nqueues, uint64_t* h_counts);
+
+/* rss_key_neighbourhood6_device on host buffers (h_counts: RSS_KEY6_NEIGHBOURS x nqueues
+ * uint64), as rss_key_neighbourhood_host: the same validation (and a NULL ctx) is refused
+ * first; n == 0 zeroes h_counts on the host. */
+int rss_key_neighbourhood6_host(rss_ctx* ctx, const rss_key6* key, const rss_tuple6* h_tuples,
+                                size_t n, uint32_t htable, uint32_t nqueues, uint64_t* h_counts);
 
 /* rss_hash6_device on host buffers: rss_hash_host's contract and path (the same staging,
  * small-batch path, pipeline and direct DMA of page-locked buffers), 36-byte tuples. */

@@ -40,9 +40,11 @@ EXPORTED_SYMBOLS = (
     "rss_csv_format6_bound", "rss_csv_format6", "rss_csv6_hash_text", "rss_csv6_hash_file",
     "rss_counts_workspace_bytes", "rss_hash_device_ws", "rss_hash6_device_ws",
     "rss_parse_dotted", "rss_parse_ipv6", "rss_key_neighbourhood_device",
-    "rss_key_neighbourhood_host",
+    "rss_key_neighbourhood_host", "rss_key_search6_device", "rss_key_search6_host",
+    "rss_key_neighbourhood6_device", "rss_key_neighbourhood6_host",
 )
 KEY_NEIGHBOURS = 128  # RSS_KEY_NEIGHBOURS: the key bits an IPv4 hash reads
+KEY6_NEIGHBOURS = 320  # RSS_KEY6_NEIGHBOURS: the key bits an IPv6 hash reads
 FIELD_SRC_IP, FIELD_DST_IP, FIELD_SRC_PORT, FIELD_DST_PORT = 1, 2, 4, 8
 FIELDS_IP, FIELDS_ALL = 3, 15
 ENOTSUP = -95
@@ -107,6 +109,12 @@ def _bind(lib):
         "rss_key_search_device": ([vp, sz, vp, sz, u32, u32, vp, vp], ctypes.c_int),
         "rss_key_neighbourhood_device": ([key_p, vp, sz, u32, u32, vp, vp], ctypes.c_int),
         "rss_key_neighbourhood_host": ([vp, key_p, vp, sz, u32, u32, vp], ctypes.c_int),
+        "rss_key_search6_device": ([vp, sz, vp, sz, u32, u32, vp, vp], ctypes.c_int),
+        "rss_key_search6_host": ([vp, vp, sz, vp, sz, u32, u32, vp], ctypes.c_int),
+        "rss_key_neighbourhood6_device": ([ctypes.POINTER(RssKey6), vp, sz, u32, u32, vp, vp],
+                                          ctypes.c_int),
+        "rss_key_neighbourhood6_host": ([vp, ctypes.POINTER(RssKey6), vp, sz, u32, u32, vp],
+                                        ctypes.c_int),
         "rss_key_select_fields": ([key_p, u32], ctypes.c_int),
         "rss_hash_device_reta": ([key_p, vp, sz, u32, vp, u32, vp, vp, vp, u32, vp], ctypes.c_int),
         "rss_hash_host_reta": ([vp, key_p, vp, sz, u32, vp, u32, vp, vp, vp, u32], ctypes.c_int),
@@ -527,6 +535,39 @@ class HostContext:
                "rss_key_neighbourhood_host")
         return out
 
+    def key_search6(self, keys, tuples, htable, nqueues):
+        """:meth:`key_search` for IPv6: ``keys`` prepared with :func:`prepare_key6`, ``tuples``
+        ``TUPLE6_DTYPE`` or ``(n, 9)`` uint32 (``rss_key_search6_host``)."""
+        htable, nqueues = queue_modulus(htable, nqueues)
+        arr = _tuples6(tuples)
+        karr = (RssKey6 * len(keys))(*keys)
+        out = np.zeros((len(keys), nqueues), dtype=np.uint64)
+        _check(self._lib.rss_key_search6_host(self._ctx, karr, len(keys), arr.ctypes.data, len(arr),
+                                              htable, nqueues, out.ctypes.data),
+               "rss_key_search6_host")
+        return out
+
+    def key_neighbourhood6(self, key6, tuples, htable, nqueues):
+        """:meth:`key_neighbourhood` for IPv6 (``rss_key_neighbourhood6_host``): uint64[320,
+        min(htable, nqueues)], row j has bit j of the 40-byte key flipped, row 319 is the key's
+        own counts."""
+        htable, nqueues = queue_modulus(htable, nqueues)
+        arr = _tuples6(tuples)
+        out = np.zeros((KEY6_NEIGHBOURS, nqueues), dtype=np.uint64)
+        _check(self._lib.rss_key_neighbourhood6_host(self._ctx, ctypes.byref(key6), arr.ctypes.data,
+                                                     len(arr), htable, nqueues, out.ctypes.data),
+               "rss_key_neighbourhood6_host")
+        return out
+
+
+def _tuples6(tuples):
+    """Contiguous IPv6 tuples: ``TUPLE6_DTYPE`` records as they are, anything else as
+    ``(n, 9)`` uint32."""
+    arr = np.ascontiguousarray(tuples)
+    if arr.dtype != TUPLE6_DTYPE:
+        arr = np.ascontiguousarray(arr, dtype=np.uint32).reshape(-1, 9)
+    return arr
+
 
 _default_ctx = None
 _ctx_lock = threading.Lock()
@@ -700,6 +741,23 @@ def key_neighbourhood_device(key, tuples_ptr, n, htable, nqueues, counts_ptr, st
     htable, nqueues = queue_modulus(htable, nqueues)
     _check(load().rss_key_neighbourhood_device(ctypes.byref(key), tuples_ptr, n, htable, nqueues,
                                                counts_ptr, stream), "rss_key_neighbourhood_device")
+
+
+def key_search6_device(windows_ptr, nkeys, tuples_ptr, n, htable, nqueues, counts_ptr,
+                       stream=None):
+    """Stream-ordered ``rss_key_search6_device`` on raw device pointers (ints): windows are
+    ``nkeys x 288`` uint32."""
+    htable, nqueues = queue_modulus(htable, nqueues)
+    _check(load().rss_key_search6_device(windows_ptr, nkeys, tuples_ptr, n, htable, nqueues,
+                                         counts_ptr, stream), "rss_key_search6_device")
+
+
+def key_neighbourhood6_device(key6, tuples_ptr, n, htable, nqueues, counts_ptr, stream=None):
+    """Stream-ordered ``rss_key_neighbourhood6_device`` on raw device pointers (ints);
+    ``counts_ptr``: ``KEY6_NEIGHBOURS x min(htable, nqueues)`` uint64."""
+    htable, nqueues = queue_modulus(htable, nqueues)
+    _check(load().rss_key_neighbourhood6_device(ctypes.byref(key6), tuples_ptr, n, htable, nqueues,
+                                                counts_ptr, stream), "rss_key_neighbourhood6_device")
 
 
 def generate_device(seed, first_index, n, tuples_ptr, stream=None):

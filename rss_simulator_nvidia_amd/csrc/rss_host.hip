@@ -88,6 +88,85 @@ int check_neighbourhood(const char* who, const rss_key* key, const rss_tuple4* t
     return RSS_OK;
 }
 
+// rss_key_neighbourhood6_device / _host
+int check_neighbourhood6(const char* who, const rss_key6* key, const rss_tuple6* tuples, size_t n,
+                         uint32_t htable, uint32_t nqueues, const uint64_t* counts) {
+    if (!key || !counts) return rss_set_error(RSS_EINVAL, "%s: key or counts is NULL", who);
+    if (n && !tuples) return rss_set_error(RSS_EINVAL, "%s: tuples is NULL", who);
+    if (htable < 1 || nqueues < 1)
+        return rss_set_error(RSS_EINVAL, "%s: htable (%u) and nqueues (%u) must be >= 1", who,
+                             htable, nqueues);
+    if (key->len < 40)
+        return rss_set_error(RSS_EINVAL,
+                             "%s: key of %u bytes: keys shorter than 40 bytes wrap, their "
+                             "neighbours are not single-word deltas", who, key->len);
+    // rss_key6 keeps no key bytes: a plain key's windows are one bit string, each the previous
+    // one moved up by a bit
+    for (int i = 0; i + 1 < RSS_INPUT6_BITS; ++i)
+        if ((key->window[i + 1] >> 1) != (key->window[i] & 0x7FFFFFFFu))
+            return rss_set_error(RSS_EINVAL,
+                                 "%s: the key's windows are not a plain Toeplitz sequence at "
+                                 "window %d (field-selected keys are not supported)", who, i);
+    return RSS_OK;
+}
+
+// rss_key_search6_device / _host
+int check_search6(const char* who, const char* what, const void* windows_or_keys, size_t nkeys,
+                  const rss_tuple6* tuples, size_t n, uint32_t htable, uint32_t nqueues,
+                  const uint64_t* counts) {
+    if (!windows_or_keys || !counts)
+        return rss_set_error(RSS_EINVAL, "%s: %s or counts is NULL", who, what);
+    if (nkeys == 0) return rss_set_error(RSS_EINVAL, "%s: no keys", who);
+    if (n && !tuples) return rss_set_error(RSS_EINVAL, "%s: tuples is NULL", who);
+    if (htable < 1 || nqueues < 1)
+        return rss_set_error(RSS_EINVAL, "%s: htable (%u) and nqueues (%u) must be >= 1", who,
+                             htable, nqueues);
+    return RSS_OK;
+}
+
+// The key-search host entries (IPv4 / IPv6, search / neighbourhood): under the context's lock
+// upload `windows` (search only; empty otherwise) and the tuples, `launch(d_windows, d_tuples,
+// d_counts, stream)`, copy count_bytes of counts back.  Synchronous.
+template <typename Tuple, typename Launch>
+int key_host_run(const char* who, rss_ctx* ctx, const std::vector<uint32_t>& windows,
+                 const Tuple* h_tuples, size_t n, size_t count_bytes, uint64_t* h_counts,
+                 Launch launch) {
+    std::lock_guard<std::mutex> lock(ctx->mu);  // (struct rss_ctx)
+    RSS_HIP_CHECK(hipSetDevice(ctx->device));
+    uint32_t* d_w = nullptr;
+    Tuple* d_t = nullptr;
+    uint64_t* d_c = nullptr;
+    hipStream_t s = ctx->stream[0];
+    auto cleanup = [&] {
+        (void)hipStreamSynchronize(s);
+        (void)hipFree(d_w);
+        (void)hipFree(d_t);
+        (void)hipFree(d_c);
+    };
+    const size_t window_bytes = windows.size() * sizeof(uint32_t);
+    hipError_t e = hipSuccess;
+    if (window_bytes) e = hipMalloc(&d_w, window_bytes);
+    if (e == hipSuccess && n) e = hipMalloc(&d_t, n * sizeof(Tuple));
+    if (e == hipSuccess) e = hipMalloc(&d_c, count_bytes);
+    if (e == hipSuccess && window_bytes)
+        e = hipMemcpyAsync(d_w, windows.data(), window_bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && n)
+        e = hipMemcpyAsync(d_t, h_tuples, n * sizeof(Tuple), hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) {
+        cleanup();
+        return rss_set_error(e == hipErrorOutOfMemory ? RSS_ENOMEM : RSS_EIO, "%s: %s", who,
+                             hipGetErrorString(e));
+    }
+    int rc = launch(d_w, d_t, d_c, s);
+    if (rc == RSS_OK) {
+        e = hipMemcpyAsync(h_counts, d_c, count_bytes, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) rc = rss_set_error(RSS_EIO, "%s: %s", who, hipGetErrorString(e));
+    }
+    cleanup();
+    return rc;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------ C ABI ---------
@@ -245,6 +324,26 @@ int rss_key_neighbourhood_device(const rss_key* key, const rss_tuple4* d_tuples,
     if (rc) return rc;
     return rss::launch_neighbourhood(key, d_tuples, n, htable, nqueues, d_counts,
                                      static_cast<hipStream_t>(stream));
+}
+
+int rss_key_search6_device(const uint32_t* d_windows, size_t nkeys, const rss_tuple6* d_tuples,
+                           size_t n, uint32_t htable, uint32_t nqueues, uint64_t* d_counts,
+                           void* stream) {
+    int rc = check_search6("rss_key_search6_device", "windows", d_windows, nkeys, d_tuples, n, htable, nqueues,
+                           d_counts);
+    if (rc) return rc;
+    return rss::launch_search6(d_windows, nkeys, d_tuples, n, htable, nqueues, d_counts,
+                               static_cast<hipStream_t>(stream));
+}
+
+int rss_key_neighbourhood6_device(const rss_key6* key, const rss_tuple6* d_tuples, size_t n,
+                                  uint32_t htable, uint32_t nqueues, uint64_t* d_counts,
+                                  void* stream) {
+    int rc = check_neighbourhood6("rss_key_neighbourhood6_device", key, d_tuples, n, htable,
+                                  nqueues, d_counts);
+    if (rc) return rc;
+    return rss::launch_neighbourhood6(key, d_tuples, n, htable, nqueues, d_counts,
+                                      static_cast<hipStream_t>(stream));
 }
 
 int rss_generate_tuples(uint64_t seed, uint64_t first_index, size_t n, rss_tuple4* d_tuples,
@@ -661,48 +760,17 @@ int rss_key_search_host(rss_ctx* ctx, const rss_key* keys, size_t nkeys,
     if (!ctx || !keys || !h_counts || nkeys == 0)
         return rss_set_error(RSS_EINVAL, "rss_key_search_host: NULL argument or no keys");
     if (n && !h_tuples) return rss_set_error(RSS_EINVAL, "rss_key_search_host: tuples is NULL");
-    std::lock_guard<std::mutex> lock(ctx->mu);  // (struct rss_ctx)
-    RSS_HIP_CHECK(hipSetDevice(ctx->device));
     std::vector<uint32_t> windows(nkeys * RSS_INPUT_BITS);
     for (size_t k = 0; k < nkeys; ++k) {
         if (keys[k].len < RSS_KEY_MIN_BYTES)
             return rss_set_error(RSS_EINVAL, "rss_key_search_host: key %zu not prepared", k);
         memcpy(&windows[k * RSS_INPUT_BITS], keys[k].window, sizeof keys[k].window);
     }
-    uint32_t* d_w = nullptr;
-    rss_tuple4* d_t = nullptr;
-    uint64_t* d_c = nullptr;
-    hipStream_t s = ctx->stream[0];
-    auto cleanup = [&] {
-        (void)hipStreamSynchronize(s);
-        (void)hipFree(d_w);
-        (void)hipFree(d_t);
-        (void)hipFree(d_c);
-    };
-    int rc = RSS_OK;
-    hipError_t e = hipMalloc(&d_w, windows.size() * sizeof(uint32_t));
-    if (e == hipSuccess && n) e = hipMalloc(&d_t, n * sizeof(rss_tuple4));
-    if (e == hipSuccess) e = hipMalloc(&d_c, nkeys * nqueues * sizeof(uint64_t));
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d_w, windows.data(), windows.size() * sizeof(uint32_t),
-                           hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && n)
-        e = hipMemcpyAsync(d_t, h_tuples, n * sizeof(rss_tuple4), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) {
-        cleanup();
-        return rss_set_error(e == hipErrorOutOfMemory ? RSS_ENOMEM : RSS_EIO, "rss_key_search_host: %s",
-                             hipGetErrorString(e));
-    }
-    rc = rss::launch_search(d_w, nkeys, d_t, n, htable, nqueues, d_c, s);
-    if (rc == RSS_OK) {
-        e = hipMemcpyAsync(h_counts, d_c, nkeys * nqueues * sizeof(uint64_t),
-                           hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess)
-            rc = rss_set_error(RSS_EIO, "rss_key_search_host: %s", hipGetErrorString(e));
-    }
-    cleanup();
-    return rc;
+    return key_host_run("rss_key_search_host", ctx, windows, h_tuples, n,
+                        nkeys * nqueues * sizeof(uint64_t), h_counts,
+                        [&](uint32_t* d_w, rss_tuple4* d_t, uint64_t* d_c, hipStream_t s) {
+                            return rss::launch_search(d_w, nkeys, d_t, n, htable, nqueues, d_c, s);
+                        });
 }
 
 int rss_key_neighbourhood_host(rss_ctx* ctx, const rss_key* key, const rss_tuple4* h_tuples,
@@ -716,33 +784,46 @@ int rss_key_neighbourhood_host(rss_ctx* ctx, const rss_key* key, const rss_tuple
         memset(h_counts, 0, count_bytes);
         return RSS_OK;
     }
-    std::lock_guard<std::mutex> lock(ctx->mu);  // (struct rss_ctx)
-    RSS_HIP_CHECK(hipSetDevice(ctx->device));
-    rss_tuple4* d_t = nullptr;
-    uint64_t* d_c = nullptr;
-    hipStream_t s = ctx->stream[0];
-    auto cleanup = [&] {
-        (void)hipStreamSynchronize(s);
-        (void)hipFree(d_t);
-        (void)hipFree(d_c);
-    };
-    hipError_t e = hipMalloc(&d_t, n * sizeof(rss_tuple4));
-    if (e == hipSuccess) e = hipMalloc(&d_c, count_bytes);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d_t, h_tuples, n * sizeof(rss_tuple4), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) {
-        cleanup();
-        return rss_set_error(e == hipErrorOutOfMemory ? RSS_ENOMEM : RSS_EIO, "%s: %s", who,
-                             hipGetErrorString(e));
+    return key_host_run(who, ctx, {}, h_tuples, n, count_bytes, h_counts,
+                        [&](uint32_t*, rss_tuple4* d_t, uint64_t* d_c, hipStream_t s) {
+                            return rss::launch_neighbourhood(key, d_t, n, htable, nqueues, d_c, s);
+                        });
+}
+
+int rss_key_search6_host(rss_ctx* ctx, const rss_key6* keys, size_t nkeys,
+                         const rss_tuple6* h_tuples, size_t n, uint32_t htable, uint32_t nqueues,
+                         uint64_t* h_counts) {
+    const char* who = "rss_key_search6_host";
+    int rc = check_search6(who, "keys", keys, nkeys, h_tuples, n, htable, nqueues, h_counts);
+    if (rc) return rc;
+    if (!ctx) return rss_set_error(RSS_EINVAL, "%s: context is NULL", who);
+    std::vector<uint32_t> windows(nkeys * RSS_INPUT6_BITS);
+    for (size_t k = 0; k < nkeys; ++k) {
+        if (keys[k].len < RSS_KEY_MIN_BYTES)
+            return rss_set_error(RSS_EINVAL, "%s: key %zu not prepared", who, k);
+        memcpy(&windows[k * RSS_INPUT6_BITS], keys[k].window, sizeof keys[k].window);
     }
-    rc = rss::launch_neighbourhood(key, d_t, n, htable, nqueues, d_c, s);
-    if (rc == RSS_OK) {
-        e = hipMemcpyAsync(h_counts, d_c, count_bytes, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) rc = rss_set_error(RSS_EIO, "%s: %s", who, hipGetErrorString(e));
+    return key_host_run(who, ctx, windows, h_tuples, n, nkeys * nqueues * sizeof(uint64_t), h_counts,
+                        [&](uint32_t* d_w, rss_tuple6* d_t, uint64_t* d_c, hipStream_t s) {
+                            return rss::launch_search6(d_w, nkeys, d_t, n, htable, nqueues, d_c, s);
+                        });
+}
+
+int rss_key_neighbourhood6_host(rss_ctx* ctx, const rss_key6* key, const rss_tuple6* h_tuples,
+                                size_t n, uint32_t htable, uint32_t nqueues, uint64_t* h_counts) {
+    const char* who = "rss_key_neighbourhood6_host";
+    int rc = check_neighbourhood6(who, key, h_tuples, n, htable, nqueues, h_counts);
+    if (rc) return rc;
+    if (!ctx) return rss_set_error(RSS_EINVAL, "%s: context is NULL", who);
+    const size_t count_bytes = sizeof(uint64_t) * RSS_KEY6_NEIGHBOURS * nqueues;
+    if (n == 0) {
+        memset(h_counts, 0, count_bytes);
+        return RSS_OK;
     }
-    cleanup();
-    return rc;
+    return key_host_run(who, ctx, {}, h_tuples, n, count_bytes, h_counts,
+                        [&](uint32_t*, rss_tuple6* d_t, uint64_t* d_c, hipStream_t s) {
+                            return rss::launch_neighbourhood6(key, d_t, n, htable, nqueues, d_c, s);
+                        });
 }
 
 }  // extern "C"

@@ -12,6 +12,13 @@
 // row 127 is the key itself.  A neighbour therefore costs no table of its own -- one base hash
 // per tuple on the conflict-free small tables (21 ds_read_b32, 2688 B of LDS), then per
 // neighbour one v_alignbit_b32, one XOR, the bucket / queue step and one LDS add.
+//
+// IPv6 (rss_key_neighbourhood6_device) is the same identity on nine words: X has 288 bits, R =
+// X << 31 has 319 in ten words, j = 0 .. 319 and row 319 is the key itself (a 40-byte key does
+// not wrap).  The base hash reads 63 small tables (8064 B), built in the kernel from the
+// key's ten words -- all that a plain Toeplitz key's 288 windows hold, carried in
+// LaunchParams::window[0 .. 9] -- and a group's deltas come from three of the tuple's nine
+// words, picked by the uniform j0 >> 5.  One kernel template serves both (kWords = 3 / 9).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -40,11 +47,22 @@ namespace {
 // 8 to 5036, 4 to 10072, 2 to 20144, 1 to 40288), and past those every (tuple, neighbour) is
 // one global atomic: exact for any H, Q, only slower.  These two run one kernel body with ng
 // at run time (kNG = 0).
-constexpr uint32_t kNbrBinBytesMax = kLdsBytes - kSmallLutBytes;  // 161152
+// IPv6: 8064 B of tables leave 155776 B --
+//     ng (private bins)   32    16    8     4     2     1
+//     queues up to        38    76    152   304   608   1217
+// then [queue][neighbour] bins with ng = 16 up to 2434 queues, 8 to 4868, 4 to 9736, 2 to 19472,
+// 1 to 38944, then global atomics.
+constexpr int kWords6 = RSS_INPUT6_BITS / 32;                                     // 9
+template <int kWords>
+constexpr uint32_t kNbrLutDwords = kWords * kSmallFields * 32;                    // 672 / 2016
+constexpr uint32_t kNbrBinBytesMax = kLdsBytes - kSmallLutBytes;                  // 161152
+constexpr uint32_t kNbr6BinBytesMax = kLdsBytes - kNbrLutDwords<kWords6> * 4;     // 155776
+static_assert(kNbrLutDwords<3> == kSmallLutDwords && kNbr6BinBytesMax == 155776, "table sizes");
 
-inline uint32_t neighbours_per_workgroup(uint64_t bytes_per_neighbour) {
+inline uint32_t neighbours_per_workgroup(uint64_t bytes_per_neighbour,
+                                         uint32_t budget = kNbrBinBytesMax) {
     uint32_t ng = 32;
-    while (ng > 1 && bytes_per_neighbour * ng > kNbrBinBytesMax) ng >>= 1;
+    while (ng > 1 && bytes_per_neighbour * ng > budget) ng >>= 1;
     return ng;
 }
 
@@ -69,15 +87,60 @@ __device__ __forceinline__ uint2 flip_span(uint32_t w0, uint32_t w1, uint32_t w2
     return make_uint2(alignbit(hi, lo, s0), hi >> s0);
 }
 
-template <int kNG, bool kHPow2, int kQMode, int kHist>
+// IPv6: the same span from nine words.  With x[-1] = x[9] = x[10] = 0, R's word k is
+// alignbit(x[k], x[k - 1], 1) for every k = 0 .. 10, so the span's two words need x[word - 1],
+// x[word], x[word + 1] -- a uniform pick among the lane's nine registers (27 v_cndmask_b32).
+__device__ __forceinline__ uint2 flip_span6(const uint32_t* w, uint32_t word, uint32_t s0) {
+    // selects on scalar conditions (a switch would turn into indexing and put w[] in scratch)
+    uint32_t a = 0u, b = 0u, c = 0u;  // tuple words word - 1, word, word + 1 (0 outside the tuple)
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)kWords6; ++k) {
+        a = word == k + 1 ? w[k] : a;
+        b = word == k ? w[k] : b;
+        c = word + 1 == k ? w[k] : c;
+    }
+    const uint32_t xa = __brev(a), xb = __brev(b), xc = __brev(c);
+    const uint32_t lo = alignbit(xb, xa, 1), hi = alignbit(xc, xb, 1);
+    return make_uint2(alignbit(hi, lo, s0), hi >> s0);
+}
+
+// the 63 IPv6 small tables from the key's ten words (key bits [32 k, 32 k + 32) in kw[k], bit
+// 319 unused): window i = key bits [i, i + 32)
+__device__ __forceinline__ void build_small_lut6(uint32_t* lut, const uint32_t* __restrict__ kw,
+                                                 uint32_t tid) {
+    for (uint32_t e = tid; e < kNbrLutDwords<kWords6>; e += kBlock) {
+        const int t = (int)(e >> 5);
+        const uint32_t v = e & 31u;
+        const int width = small_width(t % kSmallFields);
+        uint32_t x = 0;
+#pragma unroll
+        for (int b = 0; b < 5; ++b) {
+            const uint32_t i = (uint32_t)small_slice_bit(t, b);  // < 288
+            const uint64_t two = (uint64_t)kw[i >> 5] << 32 | kw[(i >> 5) + 1];
+            x ^= (b < width && ((v >> b) & 1u)) ? (uint32_t)((two << (i & 31u)) >> 32) : 0u;
+        }
+        lut[e] = (v >> width) ? 0u : x;
+    }
+}
+
+__device__ __forceinline__ uint32_t toeplitz_hash_small6(const uint32_t* __restrict__ lut,
+                                                         const uint32_t* w) {
+    const char* b = reinterpret_cast<const char*>(lut);
+    return xor3(xor3(small_word<0>(b, w[0]), small_word<7>(b, w[1]), small_word<14>(b, w[2])),
+                xor3(small_word<21>(b, w[3]), small_word<28>(b, w[4]), small_word<35>(b, w[5])),
+                xor3(small_word<42>(b, w[6]), small_word<49>(b, w[7]), small_word<56>(b, w[8])));
+}
+
+template <int kWords, int kNG, bool kHPow2, int kQMode, int kHist>
 __global__ __launch_bounds__(kBlock) void rss_key_neighbourhood_kernel(const LaunchParams p) {
-    __shared__ uint32_t lut[kSmallLutDwords];
+    __shared__ uint32_t lut[kNbrLutDwords<kWords>];
     extern __shared__ uint32_t bins[];
     const uint32_t tid = threadIdx.x;
     const uint32_t ng = kNG ? (uint32_t)kNG : p.nkeys;
     const uint32_t j0 = ng * blockIdx.y;
     const uint32_t word = j0 >> 5, s0 = j0 & 31u;
-    build_small_lut(lut, p.window, tid);
+    if constexpr (kWords == 3) build_small_lut(lut, p.window, tid);
+    else build_small_lut6(lut, p.window, tid);
     const uint32_t nbins =
         kHist == HIST_PRIVATE ? p.Q * ng * kBinCols : (kHist == HIST_SHARED ? p.Q * ng : 0u);
     for (uint32_t e = tid; e < nbins; e += kBlock) bins[e] = 0;
@@ -91,9 +154,16 @@ __global__ __launch_bounds__(kBlock) void rss_key_neighbourhood_kernel(const Lau
     // v_mul_lo_u32 (Q * row <= 161152 and b * row < 2^20 fit 24 bits)
     const int neg_q_row = -(int)(p.Q * kRowBytes);
     unsigned long long* rows = p.counts + (size_t)j0 * p.q_stride;  // row k at k * q_stride
-    auto count = [&](uint32_t w0, uint32_t w1, uint32_t w2) {
-        const uint32_t h = toeplitz_hash_small(lut, w0, w1, w2);
-        const uint2 span = flip_span(w0, w1, w2, word, s0);
+    auto count = [&](const uint32_t* w) {  // one tuple's kWords words
+        uint32_t h;
+        uint2 span;
+        if constexpr (kWords == 3) {
+            h = toeplitz_hash_small(lut, w[0], w[1], w[2]);
+            span = flip_span(w[0], w[1], w[2], word, s0);
+        } else {
+            h = toeplitz_hash_small6(lut, w);
+            span = flip_span6(w, word, s0);
+        }
         auto neighbour = [&](uint32_t k) {
             const uint32_t b = bucket_of<kHPow2>(h ^ alignbit(span.y, span.x, k), p);
             if constexpr (kHist == HIST_PRIVATE) {
@@ -126,20 +196,27 @@ __global__ __launch_bounds__(kBlock) void rss_key_neighbourhood_kernel(const Lau
     if (((uintptr_t)p.tuples & 15u) == 0) {  // 16-byte aligned: four tuples per lane
         const uint4* __restrict__ src = reinterpret_cast<const uint4*>(p.tuples);
         const uint64_t ngroups = p.n >> 2;
-        for (uint64_t g = gtid; g < ngroups; g += gstride) {
-            const uint4 a = src[3 * g + 0];
-            const uint4 b = src[3 * g + 1];
-            const uint4 c = src[3 * g + 2];
-            count(a.x, a.y, a.z);
-            count(a.w, b.x, b.y);
-            count(b.z, b.w, c.x);
-            count(c.y, c.z, c.w);
+        for (uint64_t g = gtid; g < ngroups; g += gstride) {  // kWords x 16 B = four tuples
+            uint32_t w[4 * kWords];
+#pragma unroll
+            for (int i = 0; i < kWords; ++i) {
+                const uint4 x = src[kWords * g + i];
+                w[4 * i + 0] = x.x;
+                w[4 * i + 1] = x.y;
+                w[4 * i + 2] = x.z;
+                w[4 * i + 3] = x.w;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) count(w + kWords * u);
         }
         tail_begin = ngroups << 2;
     }
     for (uint64_t i = tail_begin + gtid; i < p.n; i += gstride) {
-        const uint32_t* t = reinterpret_cast<const uint32_t*>(p.tuples) + 3 * i;
-        count(t[0], t[1], t[2]);
+        const uint32_t* t = reinterpret_cast<const uint32_t*>(p.tuples) + kWords * i;
+        uint32_t w[kWords];
+#pragma unroll
+        for (int k = 0; k < kWords; ++k) w[k] = t[k];
+        count(w);
     }
     if constexpr (kHist != HIST_GLOBAL) {
         __syncthreads();
@@ -168,31 +245,33 @@ __global__ __launch_bounds__(kBlock) void rss_zero_counts_kernel(unsigned long l
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) counts[i] = 0;
 }
 
-template <int kNG, bool kHPow2, int kHist>
+template <int kWords, int kNG, bool kHPow2, int kHist>
 KernelFn pick_nbr_qmode(int qmode) {
     switch (qmode) {
-        case QM_MASK: return rss_key_neighbourhood_kernel<kNG, kHPow2, QM_MASK, kHist>;
-        case QM_FAST8: return rss_key_neighbourhood_kernel<kNG, kHPow2, QM_FAST8, kHist>;
-        case QM_FAST16: return rss_key_neighbourhood_kernel<kNG, kHPow2, QM_FAST16, kHist>;
-        default: return rss_key_neighbourhood_kernel<kNG, kHPow2, QM_FAST32, kHist>;
+        case QM_MASK: return rss_key_neighbourhood_kernel<kWords, kNG, kHPow2, QM_MASK, kHist>;
+        case QM_FAST8: return rss_key_neighbourhood_kernel<kWords, kNG, kHPow2, QM_FAST8, kHist>;
+        case QM_FAST16: return rss_key_neighbourhood_kernel<kWords, kNG, kHPow2, QM_FAST16, kHist>;
+        default: return rss_key_neighbourhood_kernel<kWords, kNG, kHPow2, QM_FAST32, kHist>;
     }
 }
 
-template <int kNG, int kHist>
+template <int kWords, int kNG, int kHist>
 KernelFn pick_nbr_modes(bool h_pow2, int qmode) {
-    return h_pow2 ? pick_nbr_qmode<kNG, true, kHist>(qmode) : pick_nbr_qmode<kNG, false, kHist>(qmode);
+    return h_pow2 ? pick_nbr_qmode<kWords, kNG, true, kHist>(qmode)
+                  : pick_nbr_qmode<kWords, kNG, false, kHist>(qmode);
 }
 
+template <int kWords>
 KernelFn pick_nbr(int hist, uint32_t ng, bool h_pow2, int qmode) {
-    if (hist == HIST_SHARED) return pick_nbr_modes<0, HIST_SHARED>(h_pow2, qmode);
-    if (hist != HIST_PRIVATE) return pick_nbr_modes<0, HIST_GLOBAL>(h_pow2, qmode);
+    if (hist == HIST_SHARED) return pick_nbr_modes<kWords, 0, HIST_SHARED>(h_pow2, qmode);
+    if (hist != HIST_PRIVATE) return pick_nbr_modes<kWords, 0, HIST_GLOBAL>(h_pow2, qmode);
     switch (ng) {
-        case 32: return pick_nbr_modes<32, HIST_PRIVATE>(h_pow2, qmode);
-        case 16: return pick_nbr_modes<16, HIST_PRIVATE>(h_pow2, qmode);
-        case 8: return pick_nbr_modes<8, HIST_PRIVATE>(h_pow2, qmode);
-        case 4: return pick_nbr_modes<4, HIST_PRIVATE>(h_pow2, qmode);
-        case 2: return pick_nbr_modes<2, HIST_PRIVATE>(h_pow2, qmode);
-        default: return pick_nbr_modes<1, HIST_PRIVATE>(h_pow2, qmode);
+        case 32: return pick_nbr_modes<kWords, 32, HIST_PRIVATE>(h_pow2, qmode);
+        case 16: return pick_nbr_modes<kWords, 16, HIST_PRIVATE>(h_pow2, qmode);
+        case 8: return pick_nbr_modes<kWords, 8, HIST_PRIVATE>(h_pow2, qmode);
+        case 4: return pick_nbr_modes<kWords, 4, HIST_PRIVATE>(h_pow2, qmode);
+        case 2: return pick_nbr_modes<kWords, 2, HIST_PRIVATE>(h_pow2, qmode);
+        default: return pick_nbr_modes<kWords, 1, HIST_PRIVATE>(h_pow2, qmode);
     }
 }
 
@@ -214,39 +293,71 @@ inline unsigned neighbourhood_grid_x(size_t n, uint32_t q_eff, unsigned gy, int 
 // ------------------------------------------------------ launcher (rss_engine.h) --
 namespace rss {
 
-int launch_neighbourhood(const rss_key* key, const rss_tuple4* d_tuples, size_t n, uint32_t htable,
-                         uint32_t nqueues, uint64_t* d_counts, hipStream_t stream) {
+int launch_zero_counts(uint64_t* d_counts, uint64_t cells, hipStream_t stream) {
     DeviceInfo info;
     int rc = device_info(&info);
     if (rc) return rc;
-    const uint64_t cells = (uint64_t)RSS_KEY_NEIGHBOURS * nqueues;
-    const unsigned zero_grid =
-        (unsigned)std::min<uint64_t>((cells + kBlock - 1) / kBlock, 4u * (unsigned)info.cu_count);
+    const unsigned zero_grid = (unsigned)std::max<uint64_t>(
+        1, std::min<uint64_t>((cells + kBlock - 1) / kBlock, 4u * (unsigned)info.cu_count));
     hipLaunchKernelGGL(rss_zero_counts_kernel, dim3(zero_grid), dim3(kBlock), 0, stream,
                        reinterpret_cast<unsigned long long*>(d_counts), cells);
     RSS_HIP_CHECK(hipGetLastError());
-    if (n == 0) return RSS_OK;
-    LaunchParams p;
-    memset(&p, 0, sizeof p);
-    memcpy(p.window, key->window, sizeof p.window);
-    p.tuples = d_tuples;
-    p.n = n;
+    return RSS_OK;
+}
+
+// both entries: clear, then one launch of the kWords kernel over `neighbours` rows; p holds
+// the key (window) and the tuples
+template <int kWords>
+static int launch_neighbourhood_rows(LaunchParams& p, uint32_t neighbours, uint32_t budget,
+                                     uint32_t htable, uint32_t nqueues, uint64_t* d_counts,
+                                     hipStream_t stream) {
+    int rc = launch_zero_counts(d_counts, (uint64_t)neighbours * nqueues, stream);
+    if (rc || p.n == 0) return rc;
+    DeviceInfo info;
+    rc = device_info(&info);
+    if (rc) return rc;
     p.counts = reinterpret_cast<unsigned long long*>(d_counts);
     p.q_stride = nqueues;  // rows keep the caller's nqueues; queues >= min(H, Q) stay zero
     const uint32_t q_eff = effective_queues(htable, nqueues, nullptr);
     int qmode, hist;
     uint32_t bin_bytes;  // of one neighbour
-    const bool h_pow2 = setup_modes(&p, htable, q_eff, true, &qmode, &hist, &bin_bytes,
-                                    kNbrBinBytesMax);
-    const uint32_t ng = hist == HIST_GLOBAL ? 32u : neighbours_per_workgroup(bin_bytes);
+    const bool h_pow2 = setup_modes(&p, htable, q_eff, true, &qmode, &hist, &bin_bytes, budget);
+    const uint32_t ng = hist == HIST_GLOBAL ? 32u : neighbours_per_workgroup(bin_bytes, budget);
     p.nkeys = ng;
-    const unsigned gy = RSS_KEY_NEIGHBOURS / ng;
-    const unsigned gx = neighbourhood_grid_x(n, hist == HIST_PRIVATE ? q_eff : q_eff / kBinCols, gy,
+    const unsigned gy = neighbours / ng;
+    const unsigned gx = neighbourhood_grid_x(p.n, hist == HIST_PRIVATE ? q_eff : q_eff / kBinCols, gy,
                                              info.cu_count);
-    hipLaunchKernelGGL(pick_nbr(hist, ng, h_pow2, qmode), dim3(gx, gy), dim3(kBlock),
+    hipLaunchKernelGGL(pick_nbr<kWords>(hist, ng, h_pow2, qmode), dim3(gx, gy), dim3(kBlock),
                        bin_bytes * ng, stream, p);
     RSS_HIP_CHECK(hipGetLastError());
     return RSS_OK;
+}
+
+int launch_neighbourhood(const rss_key* key, const rss_tuple4* d_tuples, size_t n, uint32_t htable,
+                         uint32_t nqueues, uint64_t* d_counts, hipStream_t stream) {
+    LaunchParams p;
+    memset(&p, 0, sizeof p);
+    memcpy(p.window, key->window, sizeof p.window);
+    p.tuples = d_tuples;
+    p.n = n;
+    return launch_neighbourhood_rows<3>(p, RSS_KEY_NEIGHBOURS, kNbrBinBytesMax, htable, nqueues,
+                                        d_counts, stream);
+}
+
+int launch_neighbourhood6(const rss_key6* key, const rss_tuple6* d_tuples, size_t n,
+                          uint32_t htable, uint32_t nqueues, uint64_t* d_counts,
+                          hipStream_t stream) {
+    static_assert(RSS_KEY6_NEIGHBOURS % 32 == 0, "every ng divides the rows");
+    LaunchParams p;
+    memset(&p, 0, sizeof p);
+    // a plain Toeplitz key (checked by the caller): window 32 k is key word k; word 9 = key
+    // bits [288, 319) from the last window (bit 319 feeds no hash)
+    for (int k = 0; k < kWords6; ++k) p.window[k] = key->window[32 * k];
+    p.window[kWords6] = key->window[RSS_INPUT6_BITS - 1] << 1;
+    p.tuples = reinterpret_cast<const rss_tuple4*>(d_tuples);  // read as dwords / uint4 only
+    p.n = n;
+    return launch_neighbourhood_rows<kWords6>(p, RSS_KEY6_NEIGHBOURS, kNbr6BinBytesMax, htable,
+                                              nqueues, d_counts, stream);
 }
 
 }  // namespace rss

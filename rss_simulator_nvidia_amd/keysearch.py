@@ -15,6 +15,9 @@ of the H buckets, so a perfect key gives it ``n * slots(q) / H`` flows.
 search: Toeplitz is linear in the key, so all 128 single-bit flips of a key are scored in
 one launch from the key's own hashes (``rss_key_neighbourhood_device``), and :func:`refine`
 flips the best bit until none improves the spread.
+
+``--ipv6`` does the same for a CSV of IPv6 flows (``rss_key_search6_device``,
+``rss_key_neighbourhood6_device``: 36-byte tuples, the 320 key bits an IPv6 hash reads).
 """
 import argparse
 import random
@@ -26,7 +29,7 @@ from rss_simulator_nvidia_amd import _native
 from rss_simulator_nvidia_amd.arg_parse_types import PositiveInt
 from rss_simulator_nvidia_amd.arg_parse_types import arg_parse_type_decorator as apt_decorator
 from rss_simulator_nvidia_amd.hash_key import HASH_KEY_BYTES_LENGTH, HashKey
-from rss_simulator_nvidia_amd.ingest import pack_frame
+from rss_simulator_nvidia_amd.ingest import pack_frame, pack_frame6
 
 
 def random_keys(count, seed=0, length=HASH_KEY_BYTES_LENGTH):
@@ -70,20 +73,23 @@ def balance(counts, htable, nqueues):
             "chi2": chi2, "used": (counts > 0).sum(axis=1)}
 
 
-def evaluate(keys, tuples, htable, nqueues, ctx=None):
-    """uint64 per-queue counts ``[len(keys), Q]`` of packed ``tuples`` under every key (GPU)."""
+def evaluate(keys, tuples, htable, nqueues, ctx=None, ipv6=False):
+    """uint64 per-queue counts ``[len(keys), Q]`` of packed ``tuples`` under every key (GPU);
+    ``ipv6``: ``tuples`` are ``TUPLE6_DTYPE`` or ``(n, 9)`` uint32."""
     ctx = ctx or _native.default_context()
+    if ipv6:
+        return ctx.key_search6([_native.prepare_key6(k) for k in keys], tuples, htable, nqueues)
     prepared = [_native.prepare_key(k) for k in keys]
     return ctx.key_search(prepared, tuples, htable, nqueues)
 
 
-def search(tuples, htable, nqueues, n_keys=1024, seed=0, top=10, extra_keys=()):
+def search(tuples, htable, nqueues, n_keys=1024, seed=0, top=10, extra_keys=(), ipv6=False):
     """Rank ``n_keys`` random candidates (plus ``extra_keys``) for ``tuples``.
 
     Returns a list of dicts (best first): ``key``, ``max_load``, ``chi2``, ``used``, ``counts``.
     """
     keys = [list(k) for k in extra_keys] + random_keys(n_keys, seed)
-    counts = evaluate(keys, tuples, htable, nqueues)
+    counts = evaluate(keys, tuples, htable, nqueues, ipv6=ipv6)
     m = balance(counts, htable, nqueues)
     order = np.lexsort((m["chi2"], m["max_load"]))
     return [{"key": keys[i], "max_load": float(m["max_load"][i]), "chi2": float(m["chi2"][i]),
@@ -97,53 +103,61 @@ def flip_bit(key, j):
     return out
 
 
-def neighbourhood(key, tuples, htable, nqueues, ctx=None):
+def neighbourhood(key, tuples, htable, nqueues, ctx=None, ipv6=False):
     """uint64 counts ``[128, min(H, Q)]`` of packed ``tuples`` under every single-bit flip of
     ``key`` (GPU, one launch): row j = ``flip_bit(key, j)``; key bit 127 feeds no IPv4 hash,
-    so row 127 is ``key`` itself."""
+    so row 127 is ``key`` itself.  ``ipv6``: 320 rows over IPv6 tuples, row 319 the key itself."""
     ctx = ctx or _native.default_context()
+    if ipv6:
+        return ctx.key_neighbourhood6(_native.prepare_key6(key), tuples, htable, nqueues)
     return ctx.key_neighbourhood(_native.prepare_key(key), tuples, htable, nqueues)
 
 
-def _resident_neighbourhood(tuples, htable, nqueues):
-    """``key -> counts[128, min(H, Q)]`` on tuples uploaded once: one
-    ``rss_key_neighbourhood_device`` launch per call."""
+def _resident_neighbourhood(tuples, htable, nqueues, ipv6=False):
+    """``key -> counts[128, min(H, Q)]`` (``ipv6``: 320 rows) on tuples uploaded once: one
+    ``rss_key_neighbourhood_device`` / ``rss_key_neighbourhood6_device`` launch per call."""
     import torch
     arr = np.ascontiguousarray(tuples)
-    if arr.dtype != _native.TUPLE_DTYPE:
-        arr = np.ascontiguousarray(arr, dtype=np.uint32).reshape(-1, 3)
+    if arr.dtype != (_native.TUPLE6_DTYPE if ipv6 else _native.TUPLE_DTYPE):
+        arr = np.ascontiguousarray(arr, dtype=np.uint32).reshape(-1, 9 if ipv6 else 3)
     n = len(arr)
     dev = torch.device("cuda:%d" % _native.default_context().device)
     flat = np.ascontiguousarray(arr).view(np.int32).reshape(-1)
     d_tuples = torch.from_numpy(flat).to(dev)
     width = _native.queue_modulus(htable, nqueues)[1]
-    d_counts = torch.empty((_native.KEY_NEIGHBOURS, width), dtype=torch.int64, device=dev)
+    rows = _native.KEY6_NEIGHBOURS if ipv6 else _native.KEY_NEIGHBOURS
+    d_counts = torch.empty((rows, width), dtype=torch.int64, device=dev)
 
     def score(key):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        _native.key_neighbourhood_device(_native.prepare_key(key), d_tuples.data_ptr(), n, htable,
-                                         nqueues, d_counts.data_ptr(), stream)
+        if ipv6:
+            _native.key_neighbourhood6_device(_native.prepare_key6(key), d_tuples.data_ptr(), n,
+                                              htable, nqueues, d_counts.data_ptr(), stream)
+        else:
+            _native.key_neighbourhood_device(_native.prepare_key(key), d_tuples.data_ptr(), n,
+                                             htable, nqueues, d_counts.data_ptr(), stream)
         return d_counts.cpu().numpy().view(np.uint64)
 
     return score
 
 
-def refine(key, tuples, htable, nqueues, max_steps=64, neighbourhood=None):
+def refine(key, tuples, htable, nqueues, max_steps=64, neighbourhood=None, ipv6=False):
     """Hill-climb ``key`` over single-bit flips (steepest descent on ``(max_load, chi2)``).
 
-    Each step scores the key's 128 neighbours (one ``rss_key_neighbourhood_device`` launch
-    on tuples uploaded once; or ``neighbourhood(key) -> counts[128, Q]`` when given) with
+    Each step scores the key's 128 neighbours (``ipv6``: 320; one
+    ``rss_key_neighbourhood_device`` / ``rss_key_neighbourhood6_device`` launch on tuples
+    uploaded once; or ``neighbourhood(key) -> counts[rows, Q]`` when given) with
     :func:`balance` and flips the bit whose row has the lexicographically smallest
-    ``(max_load, chi2)``, as long as that is strictly below the key's own (row 127); it stops
+    ``(max_load, chi2)``, as long as that is strictly below the key's own (the last row); it stops
     at a local optimum or after ``max_steps`` flips.  Returns a dict: ``key``, ``max_load``,
     ``chi2``, ``used``, ``counts`` (of the returned key) and ``flips`` (the bits, in order).
     """
     key = [int(b) for b in key]
-    score = neighbourhood or _resident_neighbourhood(tuples, htable, nqueues)
+    score = neighbourhood or _resident_neighbourhood(tuples, htable, nqueues, ipv6)
     flips = []
-    own = _native.KEY_NEIGHBOURS - 1
     counts = np.asarray(score(key))
     while True:
+        own = len(counts) - 1  # the last key bit feeds no hash: the key's own counts
         m = balance(counts, htable, nqueues)
         best = int(np.lexsort((m["chi2"], m["max_load"]))[0])
         better = (m["max_load"][best], m["chi2"][best]) < (m["max_load"][own], m["chi2"][own])
@@ -155,12 +169,13 @@ def refine(key, tuples, htable, nqueues, max_steps=64, neighbourhood=None):
         counts = np.asarray(score(key))
 
 
-def load_tuples(ips_file):
+def load_tuples(ips_file, ipv6=False):
     """Packed tuples of a 4-tuple CSV: native fast path, else the pandas ingest."""
-    parsed = _native.csv_parse(np.fromfile(ips_file, dtype=np.uint8))
+    data = np.fromfile(ips_file, dtype=np.uint8)
+    parsed = _native.csv_parse6(data) if ipv6 else _native.csv_parse(data)
     if parsed is not None:
         return parsed[0]
-    return pack_frame(pd.read_csv(ips_file))
+    return (pack_frame6 if ipv6 else pack_frame)(pd.read_csv(ips_file))
 
 
 def main(argv=None):
@@ -179,13 +194,16 @@ def main(argv=None):
                    help="then hill-climb the top-ranked key (and the --key-file key) over "
                         "single-bit flips, at most STEPS flips each")
     p.add_argument("--out", metavar="PATH", help="write the best key in --key-file format")
+    p.add_argument("--ipv6", action="store_true",
+                   help="the file holds IPv6 flows (36-byte hash input, 320 key bits)")
     args = p.parse_args(argv)
-    tuples = load_tuples(args.ips_file)
+    tuples = load_tuples(args.ips_file, args.ipv6)
     extra = [args.key] if args.key else []
     ranked = search(tuples, args.htable_size, args.num_queues, args.keys, args.seed, args.top,
-                    extra)
+                    extra, args.ipv6)
     if args.key:
-        base = balance(evaluate([args.key], tuples, args.htable_size, args.num_queues),
+        base = balance(evaluate([args.key], tuples, args.htable_size, args.num_queues,
+                                ipv6=args.ipv6),
                        args.htable_size, args.num_queues)
         print("given key: max_load %.4f chi2 %.2f queues used %d"
               % (base["max_load"][0], base["chi2"][0], base["used"][0]))
@@ -194,7 +212,7 @@ def main(argv=None):
               % (key_text(r["key"]), r["max_load"], r["chi2"], r["used"]))
     if args.refine > 0:
         starts = [ranked[0]["key"]] + extra
-        score = _resident_neighbourhood(tuples, args.htable_size, args.num_queues)
+        score = _resident_neighbourhood(tuples, args.htable_size, args.num_queues, args.ipv6)
         refined = [refine(k, tuples, args.htable_size, args.num_queues, args.refine, score)
                    for k in starts]
         refined.sort(key=lambda r: (r["max_load"], r["chi2"]))

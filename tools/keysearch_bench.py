@@ -5,7 +5,14 @@ usage: python tools/keysearch_bench.py [K] [n] [uniform|flow] [H] [Q]
 The neighbourhood mode times one rss_key_neighbourhood_device launch (the 128 single-bit
 flips of one key) against the same job as one rss_key_search_device launch over the 128
 flipped keys prepared on the host, on the same resident tuples: windows of `reps` launches
-between device events, the two alternating, every window's time per launch reported."""
+between device events, the two alternating, every window's time per launch reported.
+       python tools/keysearch_bench.py --ipv6 [K] [n] [H] [Q]
+       python tools/keysearch_bench.py --ipv6 neighbourhood [n] [H] [Q]
+--ipv6 times the IPv6 entries on n resident uniform 36-byte tuples: one rss_key_search6_device
+launch over K keys against K back-to-back counts-only rss_hash6_device launches (all there was
+before it), and one rss_key_neighbourhood6_device launch against one rss_key_search6_device
+launch over the 320 host-prepared flipped keys and against 320 rss_hash6_device launches; the
+contenders alternate, `rounds` windows each, medians reported."""
 import json
 import os
 import sys
@@ -17,6 +24,77 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from rss_simulator_nvidia_amd import _native, keysearch  # noqa: E402
+
+
+def window_ms(fn, reps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def ipv6_main(argv):
+    """--ipv6 [neighbourhood] ...: see the module docstring."""
+    nbr = bool(argv) and argv[0] == "neighbourhood"
+    num = [int(a) for a in argv[1 if nbr else 0:]]
+    K = 320 if nbr else (num.pop(0) if num else 1024)
+    n, H, Q = (num + [1 << 20, 128, 24][len(num):])[:3]
+    dev = torch.device("cuda:0")
+    s = torch.cuda.current_stream(dev).cuda_stream
+    base_key = keysearch.random_keys(1, seed=7)[0]
+    keys = ([keysearch.flip_bit(base_key, j) for j in range(K)] if nbr
+            else keysearch.random_keys(K, seed=0))
+    prepared = [_native.prepare_key6(k) for k in keys]
+    win = np.stack([np.ctypeslib.as_array(k.window) for k in prepared]).astype(np.uint32)
+    windows = torch.from_numpy(win.view(np.int32)).to(dev)
+    tuples = torch.randint(0, 2**32, (9 * n,), dtype=torch.int64, device=dev,
+                           generator=torch.Generator(dev).manual_seed(1)).to(torch.int32)
+    width = _native.queue_modulus(H, Q)[1]
+    c_search = torch.empty((K, width), dtype=torch.int64, device=dev)
+    c_loop = torch.empty((K, width), dtype=torch.int64, device=dev)
+    search = lambda: _native.key_search6_device(windows.data_ptr(), K, tuples.data_ptr(), n, H, Q,  # noqa
+                                                c_search.data_ptr(), s)
+
+    def loop():  # one counts-only hash launch per key
+        for k in range(K):
+            _native.hash6_device(prepared[k], tuples.data_ptr(), n, H, Q, None, None,
+                                 c_loop[k].data_ptr(), 0, s)
+
+    contenders = {"search6": (search, 50), "hash6_loop": (loop, 3)}
+    if nbr:
+        c_nbr = torch.empty((K, width), dtype=torch.int64, device=dev)
+        base = _native.prepare_key6(base_key)
+        contenders["neighbourhood6"] = (
+            lambda: _native.key_neighbourhood6_device(base, tuples.data_ptr(), n, H, Q,
+                                                      c_nbr.data_ptr(), s), 50)
+    for fn, _ in contenders.values():  # warm, then check every contender against the loop
+        fn()
+        fn()
+    torch.cuda.synchronize()
+    assert torch.equal(c_search, c_loop) and int(c_loop.sum()) == K * n
+    assert not nbr or torch.equal(c_nbr, c_loop)
+    rounds = 7
+    times = {name: [] for name in contenders}
+    for _ in range(rounds):
+        for name, (fn, reps) in contenders.items():
+            times[name].append(window_ms(fn, reps))
+    med = {name: float(np.median(v)) for name, v in times.items()}
+    best = med["neighbourhood6" if nbr else "search6"]
+    out = {"mode": "ipv6 " + ("neighbourhood" if nbr else "search"), "keys": K, "flows": n,
+           "htable": H, "queues": Q, "window_ms": times, "median_ms": med,
+           "key_flow_evals_per_s": K * n / (best / 1e3),
+           "speedup_vs_hash6_loop": med["hash6_loop"] / best}
+    if nbr:
+        out["speedup_vs_search6"] = med["search6"] / best
+    print(json.dumps(out))
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "--ipv6":
+    ipv6_main(sys.argv[2:])
+    sys.exit(0)
 
 nbr = len(sys.argv) > 1 and sys.argv[1] == "neighbourhood"
 K = 128 if nbr else int(sys.argv[1]) if len(sys.argv) > 1 else 1024
@@ -40,17 +118,6 @@ else:
     _native.generate_device(1, 0, n, tuples.data_ptr(), s)
 run = lambda: _native.key_search_device(windows.data_ptr(), K, tuples.data_ptr(), n, H, Q,  # noqa
                                         counts.data_ptr(), s)
-
-
-def window_ms(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / reps
-
 
 if nbr:
     prepared = _native.prepare_key(base_key)
