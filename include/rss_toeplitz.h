@@ -239,6 +239,36 @@ int rss_key_neighbourhood_device(const rss_key* key, const rss_tuple4* d_tuples,
                                  void* stream);
 
 /*
+ * Key search by load: rss_key_search_device and rss_key_neighbourhood_device with a weight per
+ * tuple -- the packets or bytes of the flow -- so that a key is judged by the load it puts on
+ * each queue, not by the number of flows.  d_weights: n uint32 in device memory, d_weights[i]
+ * the weight of tuple i (an array of its own: resident tuple buffers are reused as they are).
+ * d_loads: nkeys x nqueues (search; row k = key k) or RSS_KEY_NEIGHBOURS x nqueues
+ * (neighbourhood; row j = key bit j flipped, row 127 the key itself) uint64, overwritten:
+ * d_loads[k][q] is the exact sum of d_weights[i] over the tuples with hash_k(i) % htable %
+ * nqueues == q.  Exact for any u32 weights (0 and 0xFFFFFFFF included), any htable, nqueues >=
+ * 1, any n and any 4-byte aligned pointers: the LDS bins are 64-bit (lane-private bins for 8
+ * keys per workgroup up to 77 queues, 4 up to 154, pairs up to 80, shared bins up to 2560; the
+ * neighbourhood's 32 neighbours per workgroup up to 19 queues, 16 up to 39, ... 1 up to 629,
+ * shared bins up to 20144), and past them every (tuple, key) is one global 64-bit atomic add.
+ * Columns [min(htable, nqueues), nqueues) are zero.  With every weight 1 the loads are the
+ * unweighted entry's counts.  Tuples and weights both 16-byte aligned take the 4-tuples-per-lane
+ * path.  The loads are cleared by a kernel of the same call (n == 0 only clears), so both
+ * entries can be captured into a graph.
+ * RSS_EINVAL, before any device work, with rss_last_error naming the entry and the cause:
+ * whatever the unweighted entry refuses (windows, key or loads NULL; nkeys == 0; n > 0 with
+ * tuples NULL; htable or nqueues 0; for the neighbourhood key->len < 16 or a field-selected
+ * key), and n > 0 with weights NULL.  IPv6 tuples are out of scope.
+ */
+int rss_key_search_weighted_device(const uint32_t* d_windows, size_t nkeys,
+                                   const rss_tuple4* d_tuples, const uint32_t* d_weights, size_t n,
+                                   uint32_t htable, uint32_t nqueues, uint64_t* d_loads,
+                                   void* stream);
+int rss_key_neighbourhood_weighted_device(const rss_key* key, const rss_tuple4* d_tuples,
+                                          const uint32_t* d_weights, size_t n, uint32_t htable,
+                                          uint32_t nqueues, uint64_t* d_loads, void* stream);
+
+/*
  * IPv6.  36-byte input = src addr (16 B) | dst addr (16 B) |
  * src port | dst port, the layout of the Microsoft RSS IPv6 hash; stored as nine
  * host-order words whose big-endian bytes are that input (w[0..3] src, w[4..7]
@@ -483,6 +513,20 @@ int rss_key_search_host(rss_ctx* ctx, const rss_key* keys, size_t nkeys,
  * first; n == 0 zeroes h_counts on the host. */
 int rss_key_neighbourhood_host(rss_ctx* ctx, const rss_key* key, const rss_tuple4* h_tuples,
                                size_t n, uint32_t htable, uint32_t nqueues, uint64_t* h_counts);
+
+/* rss_key_search_weighted_device / rss_key_neighbourhood_weighted_device on host buffers
+ * (keys: nkeys prepared keys; h_weights: n uint32; h_loads: nkeys x nqueues /
+ * RSS_KEY_NEIGHBOURS x nqueues uint64), as rss_key_search_host: takes the context's lock,
+ * uploads the tuples and the weights, launches, copies the loads back.  Synchronous.  The same
+ * validation (and a NULL ctx, or a key that was not prepared) is refused first; n == 0 zeroes
+ * h_loads on the host. */
+int rss_key_search_weighted_host(rss_ctx* ctx, const rss_key* keys, size_t nkeys,
+                                 const rss_tuple4* h_tuples, const uint32_t* h_weights, size_t n,
+                                 uint32_t htable, uint32_t nqueues, uint64_t* h_loads);
+int rss_key_neighbourhood_weighted_host(rss_ctx* ctx, const rss_key* key,
+                                        const rss_tuple4* h_tuples, const uint32_t* h_weights,
+                                        size_t n, uint32_t htable, uint32_t nqueues,
+                                        uint64_t* h_loads);
 
 /* rss_key_search6_device on host buffers (keys: nkeys prepared rss_key6; h_counts: nkeys x
  * nqueues uint64), as rss_key_search_host.  Synchronous.  Refuses what the device entry

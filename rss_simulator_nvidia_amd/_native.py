@@ -42,6 +42,8 @@ EXPORTED_SYMBOLS = (
     "rss_parse_dotted", "rss_parse_ipv6", "rss_key_neighbourhood_device",
     "rss_key_neighbourhood_host", "rss_key_search6_device", "rss_key_search6_host",
     "rss_key_neighbourhood6_device", "rss_key_neighbourhood6_host",
+    "rss_key_search_weighted_device", "rss_key_neighbourhood_weighted_device",
+    "rss_key_search_weighted_host", "rss_key_neighbourhood_weighted_host",
 )
 KEY_NEIGHBOURS = 128  # RSS_KEY_NEIGHBOURS: the key bits an IPv4 hash reads
 KEY6_NEIGHBOURS = 320  # RSS_KEY6_NEIGHBOURS: the key bits an IPv6 hash reads
@@ -109,6 +111,12 @@ def _bind(lib):
         "rss_key_search_device": ([vp, sz, vp, sz, u32, u32, vp, vp], ctypes.c_int),
         "rss_key_neighbourhood_device": ([key_p, vp, sz, u32, u32, vp, vp], ctypes.c_int),
         "rss_key_neighbourhood_host": ([vp, key_p, vp, sz, u32, u32, vp], ctypes.c_int),
+        "rss_key_search_weighted_device": ([vp, sz, vp, vp, sz, u32, u32, vp, vp], ctypes.c_int),
+        "rss_key_neighbourhood_weighted_device": ([key_p, vp, vp, sz, u32, u32, vp, vp],
+                                                  ctypes.c_int),
+        "rss_key_search_weighted_host": ([vp, vp, sz, vp, vp, sz, u32, u32, vp], ctypes.c_int),
+        "rss_key_neighbourhood_weighted_host": ([vp, key_p, vp, vp, sz, u32, u32, vp],
+                                                ctypes.c_int),
         "rss_key_search6_device": ([vp, sz, vp, sz, u32, u32, vp, vp], ctypes.c_int),
         "rss_key_search6_host": ([vp, vp, sz, vp, sz, u32, u32, vp], ctypes.c_int),
         "rss_key_neighbourhood6_device": ([ctypes.POINTER(RssKey6), vp, sz, u32, u32, vp, vp],
@@ -508,28 +516,44 @@ class HostContext:
         _check(rc, name)
         return counts, n.value
 
-    def key_search(self, keys, tuples, htable, nqueues):
-        """Per-queue counts (uint64[len(keys), nqueues]) of ``tuples`` under each prepared key."""
+    def key_search(self, keys, tuples, htable, nqueues, weights=None):
+        """Per-queue counts (uint64[len(keys), nqueues]) of ``tuples`` under each prepared key;
+        with ``weights`` (one u32 per tuple) the per-queue loads, the sums of the weights
+        (``rss_key_search_weighted_host``)."""
         htable, nqueues = queue_modulus(htable, nqueues)
         arr = np.ascontiguousarray(tuples)
         if arr.dtype != TUPLE_DTYPE:
             arr = np.ascontiguousarray(arr, dtype=np.uint32).reshape(-1, 3)
         karr = (RssKey * len(keys))(*keys)
         out = np.zeros((len(keys), nqueues), dtype=np.uint64)
+        if weights is not None:
+            w = tuple_weights(weights, len(arr))
+            _check(self._lib.rss_key_search_weighted_host(
+                self._ctx, karr, len(keys), arr.ctypes.data, w.ctypes.data, len(arr), htable,
+                nqueues, out.ctypes.data), "rss_key_search_weighted_host")
+            return out
         _check(self._lib.rss_key_search_host(self._ctx, karr, len(keys), arr.ctypes.data, len(arr),
                                              htable, nqueues, out.ctypes.data),
                "rss_key_search_host")
         return out
 
-    def key_neighbourhood(self, key, tuples, htable, nqueues):
+    def key_neighbourhood(self, key, tuples, htable, nqueues, weights=None):
         """Per-queue counts (uint64[128, min(htable, nqueues)]) of ``tuples`` under each
         single-bit flip of the prepared ``key`` (``rss_key_neighbourhood_host``): row j has
-        key bit j flipped (0 = MSB of byte 0), row 127 is the key's own counts."""
+        key bit j flipped (0 = MSB of byte 0), row 127 is the key's own counts.  With
+        ``weights`` (one u32 per tuple) the rows are loads, the sums of the weights
+        (``rss_key_neighbourhood_weighted_host``)."""
         htable, nqueues = queue_modulus(htable, nqueues)
         arr = np.ascontiguousarray(tuples)
         if arr.dtype != TUPLE_DTYPE:
             arr = np.ascontiguousarray(arr, dtype=np.uint32).reshape(-1, 3)
         out = np.zeros((KEY_NEIGHBOURS, nqueues), dtype=np.uint64)
+        if weights is not None:
+            w = tuple_weights(weights, len(arr))
+            _check(self._lib.rss_key_neighbourhood_weighted_host(
+                self._ctx, ctypes.byref(key), arr.ctypes.data, w.ctypes.data, len(arr), htable,
+                nqueues, out.ctypes.data), "rss_key_neighbourhood_weighted_host")
+            return out
         _check(self._lib.rss_key_neighbourhood_host(self._ctx, ctypes.byref(key), arr.ctypes.data,
                                                     len(arr), htable, nqueues, out.ctypes.data),
                "rss_key_neighbourhood_host")
@@ -558,6 +582,20 @@ class HostContext:
                                                      len(arr), htable, nqueues, out.ctypes.data),
                "rss_key_neighbourhood6_host")
         return out
+
+
+def tuple_weights(weights, n):
+    """``weights`` as contiguous uint32[n] for the weighted key-search entries: one integer in
+    [0, 2^32) per tuple, anything else is a ``ValueError``."""
+    w = np.asarray(weights)
+    if w.ndim != 1 or len(w) != n:
+        raise ValueError("weights: expected one weight per tuple (%d), got shape %s"
+                         % (n, w.shape))
+    if w.dtype.kind not in "iub":
+        raise ValueError("weights must be integers, not %s" % w.dtype)
+    if len(w) and (w.min() < 0 or w.max() > 0xFFFFFFFF):
+        raise ValueError("weights must lie in [0, 2^32)")
+    return np.ascontiguousarray(w, dtype=np.uint32)
 
 
 def _tuples6(tuples):
@@ -741,6 +779,26 @@ def key_neighbourhood_device(key, tuples_ptr, n, htable, nqueues, counts_ptr, st
     htable, nqueues = queue_modulus(htable, nqueues)
     _check(load().rss_key_neighbourhood_device(ctypes.byref(key), tuples_ptr, n, htable, nqueues,
                                                counts_ptr, stream), "rss_key_neighbourhood_device")
+
+
+def key_search_weighted_device(windows_ptr, nkeys, tuples_ptr, weights_ptr, n, htable, nqueues,
+                               loads_ptr, stream=None):
+    """Stream-ordered ``rss_key_search_weighted_device`` on raw device pointers (ints):
+    ``weights_ptr`` n uint32, ``loads_ptr`` uint64[nkeys, nqueues]."""
+    htable, nqueues = queue_modulus(htable, nqueues)
+    _check(load().rss_key_search_weighted_device(windows_ptr, nkeys, tuples_ptr, weights_ptr, n,
+                                                 htable, nqueues, loads_ptr, stream),
+           "rss_key_search_weighted_device")
+
+
+def key_neighbourhood_weighted_device(key, tuples_ptr, weights_ptr, n, htable, nqueues, loads_ptr,
+                                      stream=None):
+    """Stream-ordered ``rss_key_neighbourhood_weighted_device`` on raw device pointers (ints);
+    ``loads_ptr``: uint64[128, min(htable, nqueues)], overwritten."""
+    htable, nqueues = queue_modulus(htable, nqueues)
+    _check(load().rss_key_neighbourhood_weighted_device(ctypes.byref(key), tuples_ptr, weights_ptr,
+                                                        n, htable, nqueues, loads_ptr, stream),
+           "rss_key_neighbourhood_weighted_device")
 
 
 def key_search6_device(windows_ptr, nkeys, tuples_ptr, n, htable, nqueues, counts_ptr,

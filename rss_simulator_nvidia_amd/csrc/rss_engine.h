@@ -1,5 +1,5 @@
 // rss_engine.h -- the engine's launchers (rss_toeplitz.hip, rss_keysearch.hip,
-// rss_keysearch6.hip, rss_neighbourhood.hip) as the C ABI (rss_host.hip) calls
+// rss_keysearch6.hip, rss_neighbourhood.hip, rss_keysearch_weighted.hip) as the C ABI (rss_host.hip) calls
 // them, and the HIP error macro both use.  Internal, not ABI.
 #pragma once
 
@@ -48,6 +48,16 @@ RSS_HIDDEN int launch_search6(const uint32_t* d_windows, size_t nkeys, const rss
 RSS_HIDDEN int launch_neighbourhood6(const rss_key6* key, const rss_tuple6* d_tuples, size_t n,
                                      uint32_t htable, uint32_t nqueues, uint64_t* d_counts,
                                      hipStream_t stream);
+// rss_key_search_weighted_device / rss_key_neighbourhood_weighted_device
+// (rss_keysearch_weighted.hip; arguments validated by the caller)
+RSS_HIDDEN int launch_search_weighted(const uint32_t* d_windows, size_t nkeys,
+                                      const rss_tuple4* d_tuples, const uint32_t* d_weights,
+                                      size_t n, uint32_t htable, uint32_t nqueues,
+                                      uint64_t* d_loads, hipStream_t stream);
+RSS_HIDDEN int launch_neighbourhood_weighted(const rss_key* key, const rss_tuple4* d_tuples,
+                                             const uint32_t* d_weights, size_t n, uint32_t htable,
+                                             uint32_t nqueues, uint64_t* d_loads,
+                                             hipStream_t stream);
 // d_counts[0, cells) = 0 by a kernel (rss_neighbourhood.hip): capturable, unlike a memset node
 RSS_HIDDEN int launch_zero_counts(uint64_t* d_counts, uint64_t cells, hipStream_t stream);
 // rss_generate_tuples (n > 0, d_tuples non-NULL)

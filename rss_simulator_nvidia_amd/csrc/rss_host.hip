@@ -110,9 +110,9 @@ int check_neighbourhood6(const char* who, const rss_key6* key, const rss_tuple6*
     return RSS_OK;
 }
 
-// rss_key_search6_device / _host
+// rss_key_search6_device / _host, rss_key_search_weighted_device / _host
 int check_search6(const char* who, const char* what, const void* windows_or_keys, size_t nkeys,
-                  const rss_tuple6* tuples, size_t n, uint32_t htable, uint32_t nqueues,
+                  const void* tuples, size_t n, uint32_t htable, uint32_t nqueues,
                   const uint64_t* counts) {
     if (!windows_or_keys || !counts)
         return rss_set_error(RSS_EINVAL, "%s: %s or counts is NULL", who, what);
@@ -124,40 +124,52 @@ int check_search6(const char* who, const char* what, const void* windows_or_keys
     return RSS_OK;
 }
 
-// The key-search host entries (IPv4 / IPv6, search / neighbourhood): under the context's lock
-// upload `windows` (search only; empty otherwise) and the tuples, `launch(d_windows, d_tuples,
-// d_counts, stream)`, copy count_bytes of counts back.  Synchronous.
+// the weighted entries: n > 0 tuples need their weights
+int check_weights(const char* who, const uint32_t* weights, size_t n) {
+    if (n && !weights) return rss_set_error(RSS_EINVAL, "%s: weights is NULL", who);
+    return RSS_OK;
+}
+
+// The key-search host entries (IPv4 / IPv6, search / neighbourhood, weighted or not): under the
+// context's lock upload `windows` (search only; empty otherwise), the tuples and their weights
+// (weighted only; NULL otherwise), `launch(d_windows, d_tuples, d_weights, d_counts, stream)`,
+// copy count_bytes of counts back.  Synchronous.
 template <typename Tuple, typename Launch>
 int key_host_run(const char* who, rss_ctx* ctx, const std::vector<uint32_t>& windows,
                  const Tuple* h_tuples, size_t n, size_t count_bytes, uint64_t* h_counts,
-                 Launch launch) {
+                 Launch launch, const uint32_t* h_weights = nullptr) {
     std::lock_guard<std::mutex> lock(ctx->mu);  // (struct rss_ctx)
     RSS_HIP_CHECK(hipSetDevice(ctx->device));
     uint32_t* d_w = nullptr;
     Tuple* d_t = nullptr;
+    uint32_t* d_wt = nullptr;
     uint64_t* d_c = nullptr;
     hipStream_t s = ctx->stream[0];
     auto cleanup = [&] {
         (void)hipStreamSynchronize(s);
         (void)hipFree(d_w);
         (void)hipFree(d_t);
+        (void)hipFree(d_wt);
         (void)hipFree(d_c);
     };
     const size_t window_bytes = windows.size() * sizeof(uint32_t);
     hipError_t e = hipSuccess;
     if (window_bytes) e = hipMalloc(&d_w, window_bytes);
     if (e == hipSuccess && n) e = hipMalloc(&d_t, n * sizeof(Tuple));
+    if (e == hipSuccess && n && h_weights) e = hipMalloc(&d_wt, n * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMalloc(&d_c, count_bytes);
     if (e == hipSuccess && window_bytes)
         e = hipMemcpyAsync(d_w, windows.data(), window_bytes, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && n)
         e = hipMemcpyAsync(d_t, h_tuples, n * sizeof(Tuple), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && n && h_weights)
+        e = hipMemcpyAsync(d_wt, h_weights, n * sizeof(uint32_t), hipMemcpyHostToDevice, s);
     if (e != hipSuccess) {
         cleanup();
         return rss_set_error(e == hipErrorOutOfMemory ? RSS_ENOMEM : RSS_EIO, "%s: %s", who,
                              hipGetErrorString(e));
     }
-    int rc = launch(d_w, d_t, d_c, s);
+    int rc = launch(d_w, d_t, d_wt, d_c, s);
     if (rc == RSS_OK) {
         e = hipMemcpyAsync(h_counts, d_c, count_bytes, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -344,6 +356,29 @@ int rss_key_neighbourhood6_device(const rss_key6* key, const rss_tuple6* d_tuple
     if (rc) return rc;
     return rss::launch_neighbourhood6(key, d_tuples, n, htable, nqueues, d_counts,
                                       static_cast<hipStream_t>(stream));
+}
+
+int rss_key_search_weighted_device(const uint32_t* d_windows, size_t nkeys,
+                                   const rss_tuple4* d_tuples, const uint32_t* d_weights, size_t n,
+                                   uint32_t htable, uint32_t nqueues, uint64_t* d_loads,
+                                   void* stream) {
+    const char* who = "rss_key_search_weighted_device";
+    int rc = check_search6(who, "windows", d_windows, nkeys, d_tuples, n, htable, nqueues, d_loads);
+    if (rc == RSS_OK) rc = check_weights(who, d_weights, n);
+    if (rc) return rc;
+    return rss::launch_search_weighted(d_windows, nkeys, d_tuples, d_weights, n, htable, nqueues,
+                                       d_loads, static_cast<hipStream_t>(stream));
+}
+
+int rss_key_neighbourhood_weighted_device(const rss_key* key, const rss_tuple4* d_tuples,
+                                          const uint32_t* d_weights, size_t n, uint32_t htable,
+                                          uint32_t nqueues, uint64_t* d_loads, void* stream) {
+    const char* who = "rss_key_neighbourhood_weighted_device";
+    int rc = check_neighbourhood(who, key, d_tuples, n, htable, nqueues, d_loads);
+    if (rc == RSS_OK) rc = check_weights(who, d_weights, n);
+    if (rc) return rc;
+    return rss::launch_neighbourhood_weighted(key, d_tuples, d_weights, n, htable, nqueues, d_loads,
+                                              static_cast<hipStream_t>(stream));
 }
 
 int rss_generate_tuples(uint64_t seed, uint64_t first_index, size_t n, rss_tuple4* d_tuples,
@@ -768,7 +803,7 @@ int rss_key_search_host(rss_ctx* ctx, const rss_key* keys, size_t nkeys,
     }
     return key_host_run("rss_key_search_host", ctx, windows, h_tuples, n,
                         nkeys * nqueues * sizeof(uint64_t), h_counts,
-                        [&](uint32_t* d_w, rss_tuple4* d_t, uint64_t* d_c, hipStream_t s) {
+                        [&](uint32_t* d_w, rss_tuple4* d_t, uint32_t*, uint64_t* d_c, hipStream_t s) {
                             return rss::launch_search(d_w, nkeys, d_t, n, htable, nqueues, d_c, s);
                         });
 }
@@ -785,9 +820,58 @@ int rss_key_neighbourhood_host(rss_ctx* ctx, const rss_key* key, const rss_tuple
         return RSS_OK;
     }
     return key_host_run(who, ctx, {}, h_tuples, n, count_bytes, h_counts,
-                        [&](uint32_t*, rss_tuple4* d_t, uint64_t* d_c, hipStream_t s) {
+                        [&](uint32_t*, rss_tuple4* d_t, uint32_t*, uint64_t* d_c, hipStream_t s) {
                             return rss::launch_neighbourhood(key, d_t, n, htable, nqueues, d_c, s);
                         });
+}
+
+int rss_key_search_weighted_host(rss_ctx* ctx, const rss_key* keys, size_t nkeys,
+                                 const rss_tuple4* h_tuples, const uint32_t* h_weights, size_t n,
+                                 uint32_t htable, uint32_t nqueues, uint64_t* h_loads) {
+    const char* who = "rss_key_search_weighted_host";
+    int rc = check_search6(who, "keys", keys, nkeys, h_tuples, n, htable, nqueues, h_loads);
+    if (rc == RSS_OK) rc = check_weights(who, h_weights, n);
+    if (rc) return rc;
+    if (!ctx) return rss_set_error(RSS_EINVAL, "%s: context is NULL", who);
+    std::vector<uint32_t> windows(nkeys * RSS_INPUT_BITS);
+    for (size_t k = 0; k < nkeys; ++k) {
+        if (keys[k].len < RSS_KEY_MIN_BYTES)
+            return rss_set_error(RSS_EINVAL, "%s: key %zu not prepared", who, k);
+        memcpy(&windows[k * RSS_INPUT_BITS], keys[k].window, sizeof keys[k].window);
+    }
+    const size_t load_bytes = nkeys * nqueues * sizeof(uint64_t);
+    if (n == 0) {
+        memset(h_loads, 0, load_bytes);
+        return RSS_OK;
+    }
+    return key_host_run(who, ctx, windows, h_tuples, n, load_bytes, h_loads,
+                        [&](uint32_t* d_w, rss_tuple4* d_t, uint32_t* d_wt, uint64_t* d_c,
+                            hipStream_t s) {
+                            return rss::launch_search_weighted(d_w, nkeys, d_t, d_wt, n, htable,
+                                                               nqueues, d_c, s);
+                        }, h_weights);
+}
+
+int rss_key_neighbourhood_weighted_host(rss_ctx* ctx, const rss_key* key,
+                                        const rss_tuple4* h_tuples, const uint32_t* h_weights,
+                                        size_t n, uint32_t htable, uint32_t nqueues,
+                                        uint64_t* h_loads) {
+    const char* who = "rss_key_neighbourhood_weighted_host";
+    int rc = check_neighbourhood(who, key, h_tuples, n, htable, nqueues, h_loads);
+    if (rc == RSS_OK) rc = check_weights(who, h_weights, n);
+    if (rc) return rc;
+    if (!ctx) return rss_set_error(RSS_EINVAL, "%s: context is NULL", who);
+    const size_t load_bytes = sizeof(uint64_t) * RSS_KEY_NEIGHBOURS * nqueues;
+    if (n == 0) {
+        memset(h_loads, 0, load_bytes);
+        return RSS_OK;
+    }
+    return key_host_run(who, ctx, {}, h_tuples, n, load_bytes, h_loads,
+                        [&](uint32_t*, rss_tuple4* d_t, uint32_t* d_wt, uint64_t* d_c,
+                            hipStream_t s) {
+                            return rss::launch_neighbourhood_weighted(key, d_t, d_wt, n, htable,
+                                                                      nqueues, d_c, s);
+                        }, h_weights);
 }
 
 int rss_key_search6_host(rss_ctx* ctx, const rss_key6* keys, size_t nkeys,
@@ -804,7 +888,7 @@ int rss_key_search6_host(rss_ctx* ctx, const rss_key6* keys, size_t nkeys,
         memcpy(&windows[k * RSS_INPUT6_BITS], keys[k].window, sizeof keys[k].window);
     }
     return key_host_run(who, ctx, windows, h_tuples, n, nkeys * nqueues * sizeof(uint64_t), h_counts,
-                        [&](uint32_t* d_w, rss_tuple6* d_t, uint64_t* d_c, hipStream_t s) {
+                        [&](uint32_t* d_w, rss_tuple6* d_t, uint32_t*, uint64_t* d_c, hipStream_t s) {
                             return rss::launch_search6(d_w, nkeys, d_t, n, htable, nqueues, d_c, s);
                         });
 }
@@ -821,7 +905,7 @@ int rss_key_neighbourhood6_host(rss_ctx* ctx, const rss_key6* key, const rss_tup
         return RSS_OK;
     }
     return key_host_run(who, ctx, {}, h_tuples, n, count_bytes, h_counts,
-                        [&](uint32_t*, rss_tuple6* d_t, uint64_t* d_c, hipStream_t s) {
+                        [&](uint32_t*, rss_tuple6* d_t, uint32_t*, uint64_t* d_c, hipStream_t s) {
                             return rss::launch_neighbourhood6(key, d_t, n, htable, nqueues, d_c, s);
                         });
 }

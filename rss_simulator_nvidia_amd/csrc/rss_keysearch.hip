@@ -12,6 +12,7 @@
 
 #include "rss_engine.h"
 #include "rss_kernel_common.h"
+#include "rss_keysearch_tables.h"
 
 namespace {
 
@@ -37,132 +38,8 @@ namespace {
 //   evaluations/s at H = 100, Q = 24 (profiles/archive/r04/small_tables/keysearch_configs.jsonl).
 // blockIdx.y selects the pair; each workgroup histograms its grid-stride share of the
 // tuples into counts rows 2y, 2y+1.  With the tuples resident in the 256 MiB Infinity Cache
-// the re-reads stay on die.
-constexpr uint32_t kPairLutBytes = kSmallTables * 256;            // 5376 (packed kernel)
-constexpr uint32_t kPackedBinBytesMax = kLdsBytes - kPairLutBytes;  // 154.75 KiB for the bins
-constexpr uint32_t kWidePairLutBytes = 6 * 16384 + 3 * 8192;     // 122880 (pair kernel)
-constexpr uint32_t kWidePairBinBytesMax = kLdsBytes - kWidePairLutBytes;  // 40 KiB, 2 x Q bins
-
-__host__ __device__ constexpr int wide_pair_width(int t) {
-    return (t == 3 || t == 4 || t == 8) ? 10 : 11;
-}
-__host__ __device__ constexpr uint32_t wide_pair_table(int t) {  // byte offset
-    return t == 0 ? 0u : t == 1 ? 16384u : t == 2 ? 32768u : t == 3 ? 49152u : t == 4 ? 57344u
-         : t == 5 ? 65536u : t == 6 ? 81920u : t == 7 ? 98304u : 114688u;
-}
-// input bit (0 = MSB of the source ip) feeding bit b of table t's index
-__host__ __device__ constexpr int wide_pair_bit(int t, int b) {
-    return t == 0 ? 31 - b : t == 1 ? 20 - b : t == 2 ? 63 - b
-         : t == 3 ? (b < 5 ? 84 - b : 73 - b)
-         : t == 4 ? 9 - b : t == 5 ? 52 - b : t == 6 ? 95 - b : t == 7 ? 79 - b : 41 - b;
-}
-
-template <int kT>
-__device__ __forceinline__ void build_wide_pair_table(uint2* lut, const uint32_t* __restrict__ wa,
-                                                      const uint32_t* __restrict__ wb, uint32_t tid) {
-    uint32_t a = 0, b = 0;
-#pragma unroll
-    for (int j = 0; j < 10; ++j) {
-        const bool set = (tid >> j) & 1u;
-        a ^= set ? wa[wide_pair_bit(kT, j)] : 0u;
-        b ^= set ? wb[wide_pair_bit(kT, j)] : 0u;
-    }
-    uint2* dst = lut + wide_pair_table(kT) / 8;
-    dst[tid] = make_uint2(a, b);
-    if constexpr (wide_pair_width(kT) == 11)
-        dst[tid + 1024] = make_uint2(a ^ wa[wide_pair_bit(kT, 10)], b ^ wb[wide_pair_bit(kT, 10)]);
-}
-
-// byte address of wide table t's entry: 2 VALU (4 for the two-field t3); tables 5..8 take
-// their 64 KiB base from the opaque register `hi`
-template <int kT>
-__device__ __forceinline__ uint32_t wide_pair_offset(uint32_t w0, uint32_t w1, uint32_t w2,
-                                                     uint32_t hi) {
-    if constexpr (kT == 0) return (w0 << 3) & 0x3FF8u;
-    if constexpr (kT == 1) return (w0 >> 8) & 0x3FF8u;
-    if constexpr (kT == 2) return (w1 << 3) & 0x3FF8u;
-    if constexpr (kT == 3) return ((w2 >> 8) & 0xF8u) | ((w2 >> 19) & 0x1F00u);
-    if constexpr (kT == 4) return (w0 >> 19) & 0x1FF8u;
-    if constexpr (kT == 5) return ((w1 >> 8) & 0x3FF8u) | hi;
-    if constexpr (kT == 6) return ((w2 << 3) & 0x3FF8u) | hi;
-    if constexpr (kT == 7) return ((w2 >> 13) & 0x3FF8u) | hi;
-    return ((w1 >> 19) & 0x1FF8u) | hi;
-}
-
-template <int kT>
-__device__ __forceinline__ uint2 wide_pair_term(const char* lut, uint32_t w0, uint32_t w1,
-                                                uint32_t w2, uint32_t hi) {
-    constexpr uint32_t kImm = wide_pair_table(kT) & 0xFFFFu;
-    return *reinterpret_cast<const uint2*>(lut + kImm + wide_pair_offset<kT>(w0, w1, w2, hi));
-}
-
-// (hash under key A, hash under key B) of one tuple on the wide tables
-__device__ __forceinline__ uint2 toeplitz_hash_wide_pair(const uint2* __restrict__ lut, uint32_t w0,
-                                                         uint32_t w1, uint32_t w2, uint32_t hi) {
-    const char* base = reinterpret_cast<const char*>(lut);
-    const uint2 t0 = wide_pair_term<0>(base, w0, w1, w2, hi), t1 = wide_pair_term<1>(base, w0, w1, w2, hi);
-    const uint2 t2 = wide_pair_term<2>(base, w0, w1, w2, hi), t3 = wide_pair_term<3>(base, w0, w1, w2, hi);
-    const uint2 t4 = wide_pair_term<4>(base, w0, w1, w2, hi), t5 = wide_pair_term<5>(base, w0, w1, w2, hi);
-    const uint2 t6 = wide_pair_term<6>(base, w0, w1, w2, hi), t7 = wide_pair_term<7>(base, w0, w1, w2, hi);
-    const uint2 t8 = wide_pair_term<8>(base, w0, w1, w2, hi);
-    return make_uint2(xor3(xor3(t0.x, t1.x, t2.x), xor3(t3.x, t4.x, t5.x), xor3(t6.x, t7.x, t8.x)),
-                      xor3(xor3(t0.y, t1.y, t2.y), xor3(t3.y, t4.y, t5.y), xor3(t6.y, t7.y, t8.y)));
-}
-
-// entry e = 32 t + v of the 21 pair tables: (XOR of key A's windows, of key B's) over the
-// input bits set in v; `win(i)` gives the two keys' window i as a uint2
-template <typename Win>
-__device__ __forceinline__ void build_small_pair_lut(uint2* lut, Win win, uint32_t tid) {
-    for (uint32_t e = tid; e < kSmallLutDwords; e += kBlock) {
-        const int t = (int)(e >> 5);
-        const uint32_t v = e & 31u;
-        const int width = small_width(t % kSmallFields);
-        uint32_t a = 0, b = 0;
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            if (j < width && ((v >> j) & 1u)) {
-                const uint2 w = win(small_slice_bit(t, j));
-                a ^= w.x;
-                b ^= w.y;
-            }
-        }
-        lut[e] = (v >> width) ? make_uint2(0u, 0u) : make_uint2(a, b);
-    }
-}
-
-// table 7k + j's 8-byte term for word w (= word k): the field moved to byte offset 8 * field
-template <int kT>
-__device__ __forceinline__ uint2 small_pair_term(const char* lut, uint32_t w) {
-    constexpr int j = kT % kSmallFields, o = 5 * j;
-    uint32_t off;
-    if constexpr (j == 0)
-        off = (w << 3) & 0xF8u;
-    else if constexpr (j == 6)
-        off = (w >> 27) & 0x18u;
-    else
-        off = (w >> (o - 3)) & 0xF8u;
-    return *reinterpret_cast<const uint2*>(lut + kT * 256 + off);
-}
-
-template <int kBase>
-__device__ __forceinline__ uint2 small_pair_word(const char* lut, uint32_t w) {  // 7 terms
-    const uint2 t0 = small_pair_term<kBase + 0>(lut, w), t1 = small_pair_term<kBase + 1>(lut, w);
-    const uint2 t2 = small_pair_term<kBase + 2>(lut, w), t3 = small_pair_term<kBase + 3>(lut, w);
-    const uint2 t4 = small_pair_term<kBase + 4>(lut, w), t5 = small_pair_term<kBase + 5>(lut, w);
-    const uint2 t6 = small_pair_term<kBase + 6>(lut, w);
-    return make_uint2(xor3(xor3(t0.x, t1.x, t2.x), xor3(t3.x, t4.x, t5.x), t6.x),
-                      xor3(xor3(t0.y, t1.y, t2.y), xor3(t3.y, t4.y, t5.y), t6.y));
-}
-
-// (hash under key A, hash under key B) of one tuple (packed kernel: 8 / 4 keys' low bits)
-__device__ __forceinline__ uint2 toeplitz_hash_pair(const uint2* __restrict__ lut, uint32_t w0,
-                                                    uint32_t w1, uint32_t w2) {
-    const char* base = reinterpret_cast<const char*>(lut);
-    const uint2 a = small_pair_word<0>(base, w0), b = small_pair_word<7>(base, w1);
-    const uint2 c = small_pair_word<14>(base, w2);
-    return make_uint2(xor3(a.x, b.x, c.x), xor3(a.y, b.y, c.y));
-}
-
+// the re-reads stay on die.  (The tables and their hashes: rss_keysearch_tables.h, shared
+// with the weighted kernels of rss_keysearch_weighted.hip.)
 template <bool kHPow2, int kQMode, int kHist>
 __device__ __forceinline__ void count_pair(uint32_t* bins_a, uint32_t* bins_b, uint2 h,
                                            uint32_t col, const LaunchParams& qa,
@@ -256,7 +133,6 @@ __global__ __launch_bounds__(kBlock) void rss_key_search_kernel(const LaunchPara
 // LDS add.
 // Bins are [q][key][lane column]: the key's offset is a ds_add immediate and every
 // half-wave's adds stay conflict-free.
-constexpr uint32_t kPackedPrepBytes = RSS_INPUT_BITS * 8;  // packed windows, before the bins
 
 template <int kLaneBits, int kQMode, bool kVec4>
 __global__ __launch_bounds__(kBlock) void rss_key_search_packed_kernel(const LaunchParams p) {
@@ -374,12 +250,6 @@ KernelFn pick_search(int qmode, int hist, bool vec4) {
         case QM_FAST16: return pick_search_hist<kHPow2, QM_FAST16>(hist, vec4);
         default: return pick_search_hist<kHPow2, QM_FAST32>(hist, vec4);
     }
-}
-
-// ~256K tuples per workgroup amortise its 120 KiB table build
-inline unsigned search_grid_x(size_t n, int cu_count) {
-    const uint64_t slices = (n + (1u << 18) - 1) >> 18;
-    return (unsigned)(slices < (uint64_t)cu_count ? slices : cu_count);
 }
 
 template <int kLaneBits, int kQMode>

@@ -27,6 +27,7 @@
 
 #include "rss_engine.h"
 #include "rss_kernel_common.h"
+#include "rss_keysearch_tables.h"
 
 namespace {
 
@@ -55,37 +56,8 @@ namespace {
 constexpr int kWords6 = RSS_INPUT6_BITS / 32;                                     // 9
 template <int kWords>
 constexpr uint32_t kNbrLutDwords = kWords * kSmallFields * 32;                    // 672 / 2016
-constexpr uint32_t kNbrBinBytesMax = kLdsBytes - kSmallLutBytes;                  // 161152
 constexpr uint32_t kNbr6BinBytesMax = kLdsBytes - kNbrLutDwords<kWords6> * 4;     // 155776
 static_assert(kNbrLutDwords<3> == kSmallLutDwords && kNbr6BinBytesMax == 155776, "table sizes");
-
-inline uint32_t neighbours_per_workgroup(uint64_t bytes_per_neighbour,
-                                         uint32_t budget = kNbrBinBytesMax) {
-    uint32_t ng = 32;
-    while (ng > 1 && bytes_per_neighbour * ng > budget) ng >>= 1;
-    return ng;
-}
-
-__device__ __forceinline__ uint32_t alignbit(uint32_t hi, uint32_t lo, uint32_t s) {
-    return __builtin_amdgcn_alignbit(hi, lo, s);  // low word of {hi, lo} >> (s & 31)
-}
-
-// bits [32 word + s0, 32 word + s0 + 64) of R for one tuple: neighbour j0 + k's delta is the
-// low word of this span >> k  (s0 + k <= 31)
-__device__ __forceinline__ uint2 flip_span(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t word,
-                                           uint32_t s0) {
-    const uint32_t x0 = __brev(w0), x1 = __brev(w1), x2 = __brev(w2);
-    // R = X << 31 as words r0 .. r3 (r4 = 0)
-    const uint32_t r0 = x0 << 31, r1 = alignbit(x1, x0, 1), r2 = alignbit(x2, x1, 1), r3 = x2 >> 1;
-    uint32_t lo, hi;
-    switch (word) {  // uniform
-        case 0: lo = r0; hi = r1; break;
-        case 1: lo = r1; hi = r2; break;
-        case 2: lo = r2; hi = r3; break;
-        default: lo = r3; hi = 0u; break;
-    }
-    return make_uint2(alignbit(hi, lo, s0), hi >> s0);
-}
 
 // IPv6: the same span from nine words.  With x[-1] = x[9] = x[10] = 0, R's word k is
 // alignbit(x[k], x[k - 1], 1) for every k = 0 .. 10, so the span's two words need x[word - 1],
@@ -273,19 +245,6 @@ KernelFn pick_nbr(int hist, uint32_t ng, bool h_pow2, int qmode) {
         case 2: return pick_nbr_modes<kWords, 2, HIST_PRIVATE>(h_pow2, qmode);
         default: return pick_nbr_modes<kWords, 1, HIST_PRIVATE>(h_pow2, qmode);
     }
-}
-
-// Workgroups along x.  A workgroup's fixed cost is its bins: q * ng * 32 dwords cleared and
-// summed again by 1024 lanes, q * ng / 16 LDS accesses per lane, against ng adds per tuple --
-// so q / 2 tuples per lane (at least 16: four 4-tuple loads) keep it near a tenth of the work.
-// That is far less than the search kernels' 256K tuples per workgroup (their 120 KiB table
-// build), and 2^20 tuples already fill the device: 64 x 4 workgroups at Q = 24.  No more than
-// one round of workgroups (cu_count / y), since each may hold a CU's whole LDS.
-inline unsigned neighbourhood_grid_x(size_t n, uint32_t q_eff, unsigned gy, int cu_count) {
-    const uint64_t per_wg = (uint64_t)kBlock * std::max<uint32_t>(16u, q_eff / 2);
-    const uint64_t slices = (n + per_wg - 1) / per_wg;
-    const uint64_t cap = std::max<uint64_t>(1, (uint64_t)cu_count / gy);
-    return (unsigned)std::min(slices, cap);
 }
 
 }  // namespace

@@ -18,6 +18,11 @@ flips the best bit until none improves the spread.
 
 ``--ipv6`` does the same for a CSV of IPv6 flows (``rss_key_search6_device``,
 ``rss_key_neighbourhood6_device``: 36-byte tuples, the 320 key bits an IPv6 hash reads).
+
+``--weight-column NAME`` (a CSV column of packets or bytes per flow) or ``--pcap PATH`` (a
+capture: its unique flows, weighted by their packets) rank and refine by the **load** each
+key puts on a queue instead of the number of flows (``rss_key_search_weighted_device``,
+``rss_key_neighbourhood_weighted_device``; IPv4 flows).
 """
 import argparse
 import random
@@ -59,6 +64,10 @@ def balance(counts, htable, nqueues):
     Returns a dict of arrays: ``max_load`` = max over reachable queues of
     observed / ideal flows (1.0 is perfect), ``chi2`` = sum of (observed - ideal)^2 /
     ideal, and ``used`` = number of non-empty queues.
+
+    Every row is normalised by its own sum, so rows of weighted loads (``weights=`` in
+    :func:`evaluate`, :func:`neighbourhood`, ...) are ranked unchanged: "flows" then reads
+    packets or bytes, whatever the weights count.
     """
     counts = np.atleast_2d(np.asarray(counts, dtype=np.float64))
     n = counts.sum(axis=1, keepdims=True)
@@ -73,23 +82,35 @@ def balance(counts, htable, nqueues):
             "chi2": chi2, "used": (counts > 0).sum(axis=1)}
 
 
-def evaluate(keys, tuples, htable, nqueues, ctx=None, ipv6=False):
+def _no_ipv6_weights(ipv6, weights):
+    if ipv6 and weights is not None:
+        raise NotImplementedError("weights with ipv6=True: the weighted key-search kernels "
+                                  "serve IPv4 tuples only")
+
+
+def evaluate(keys, tuples, htable, nqueues, ctx=None, ipv6=False, weights=None):
     """uint64 per-queue counts ``[len(keys), Q]`` of packed ``tuples`` under every key (GPU);
-    ``ipv6``: ``tuples`` are ``TUPLE6_DTYPE`` or ``(n, 9)`` uint32."""
+    ``ipv6``: ``tuples`` are ``TUPLE6_DTYPE`` or ``(n, 9)`` uint32.  ``weights`` (one integer
+    in [0, 2^32) per tuple, IPv4 only): per-queue loads, the sums of the weights, instead."""
+    _no_ipv6_weights(ipv6, weights)
     ctx = ctx or _native.default_context()
     if ipv6:
         return ctx.key_search6([_native.prepare_key6(k) for k in keys], tuples, htable, nqueues)
     prepared = [_native.prepare_key(k) for k in keys]
-    return ctx.key_search(prepared, tuples, htable, nqueues)
+    if weights is None:
+        return ctx.key_search(prepared, tuples, htable, nqueues)
+    return ctx.key_search(prepared, tuples, htable, nqueues, weights=weights)
 
 
-def search(tuples, htable, nqueues, n_keys=1024, seed=0, top=10, extra_keys=(), ipv6=False):
-    """Rank ``n_keys`` random candidates (plus ``extra_keys``) for ``tuples``.
+def search(tuples, htable, nqueues, n_keys=1024, seed=0, top=10, extra_keys=(), ipv6=False,
+           weights=None):
+    """Rank ``n_keys`` random candidates (plus ``extra_keys``) for ``tuples``, by flows or with
+    ``weights`` by load.
 
     Returns a list of dicts (best first): ``key``, ``max_load``, ``chi2``, ``used``, ``counts``.
     """
     keys = [list(k) for k in extra_keys] + random_keys(n_keys, seed)
-    counts = evaluate(keys, tuples, htable, nqueues, ipv6=ipv6)
+    counts = evaluate(keys, tuples, htable, nqueues, ipv6=ipv6, weights=weights)
     m = balance(counts, htable, nqueues)
     order = np.lexsort((m["chi2"], m["max_load"]))
     return [{"key": keys[i], "max_load": float(m["max_load"][i]), "chi2": float(m["chi2"][i]),
@@ -103,19 +124,26 @@ def flip_bit(key, j):
     return out
 
 
-def neighbourhood(key, tuples, htable, nqueues, ctx=None, ipv6=False):
+def neighbourhood(key, tuples, htable, nqueues, ctx=None, ipv6=False, weights=None):
     """uint64 counts ``[128, min(H, Q)]`` of packed ``tuples`` under every single-bit flip of
     ``key`` (GPU, one launch): row j = ``flip_bit(key, j)``; key bit 127 feeds no IPv4 hash,
-    so row 127 is ``key`` itself.  ``ipv6``: 320 rows over IPv6 tuples, row 319 the key itself."""
+    so row 127 is ``key`` itself.  ``ipv6``: 320 rows over IPv6 tuples, row 319 the key itself.
+    ``weights`` (IPv4 only): the rows are loads, the sums of the tuples' weights."""
+    _no_ipv6_weights(ipv6, weights)
     ctx = ctx or _native.default_context()
     if ipv6:
         return ctx.key_neighbourhood6(_native.prepare_key6(key), tuples, htable, nqueues)
-    return ctx.key_neighbourhood(_native.prepare_key(key), tuples, htable, nqueues)
+    if weights is None:
+        return ctx.key_neighbourhood(_native.prepare_key(key), tuples, htable, nqueues)
+    return ctx.key_neighbourhood(_native.prepare_key(key), tuples, htable, nqueues,
+                                 weights=weights)
 
 
-def _resident_neighbourhood(tuples, htable, nqueues, ipv6=False):
+def _resident_neighbourhood(tuples, htable, nqueues, ipv6=False, weights=None):
     """``key -> counts[128, min(H, Q)]`` (``ipv6``: 320 rows) on tuples uploaded once: one
-    ``rss_key_neighbourhood_device`` / ``rss_key_neighbourhood6_device`` launch per call."""
+    ``rss_key_neighbourhood_device`` / ``rss_key_neighbourhood6_device`` launch per call; with
+    ``weights``, uploaded once beside the tuples, ``rss_key_neighbourhood_weighted_device``."""
+    _no_ipv6_weights(ipv6, weights)
     import torch
     arr = np.ascontiguousarray(tuples)
     if arr.dtype != (_native.TUPLE6_DTYPE if ipv6 else _native.TUPLE_DTYPE):
@@ -124,6 +152,8 @@ def _resident_neighbourhood(tuples, htable, nqueues, ipv6=False):
     dev = torch.device("cuda:%d" % _native.default_context().device)
     flat = np.ascontiguousarray(arr).view(np.int32).reshape(-1)
     d_tuples = torch.from_numpy(flat).to(dev)
+    if weights is not None:
+        d_weights = torch.from_numpy(_native.tuple_weights(weights, n).view(np.int32)).to(dev)
     width = _native.queue_modulus(htable, nqueues)[1]
     rows = _native.KEY6_NEIGHBOURS if ipv6 else _native.KEY_NEIGHBOURS
     d_counts = torch.empty((rows, width), dtype=torch.int64, device=dev)
@@ -133,6 +163,10 @@ def _resident_neighbourhood(tuples, htable, nqueues, ipv6=False):
         if ipv6:
             _native.key_neighbourhood6_device(_native.prepare_key6(key), d_tuples.data_ptr(), n,
                                               htable, nqueues, d_counts.data_ptr(), stream)
+        elif weights is not None:
+            _native.key_neighbourhood_weighted_device(
+                _native.prepare_key(key), d_tuples.data_ptr(), d_weights.data_ptr(), n, htable,
+                nqueues, d_counts.data_ptr(), stream)
         else:
             _native.key_neighbourhood_device(_native.prepare_key(key), d_tuples.data_ptr(), n,
                                              htable, nqueues, d_counts.data_ptr(), stream)
@@ -141,7 +175,8 @@ def _resident_neighbourhood(tuples, htable, nqueues, ipv6=False):
     return score
 
 
-def refine(key, tuples, htable, nqueues, max_steps=64, neighbourhood=None, ipv6=False):
+def refine(key, tuples, htable, nqueues, max_steps=64, neighbourhood=None, ipv6=False,
+           weights=None):
     """Hill-climb ``key`` over single-bit flips (steepest descent on ``(max_load, chi2)``).
 
     Each step scores the key's 128 neighbours (``ipv6``: 320; one
@@ -151,9 +186,12 @@ def refine(key, tuples, htable, nqueues, max_steps=64, neighbourhood=None, ipv6=
     ``(max_load, chi2)``, as long as that is strictly below the key's own (the last row); it stops
     at a local optimum or after ``max_steps`` flips.  Returns a dict: ``key``, ``max_load``,
     ``chi2``, ``used``, ``counts`` (of the returned key) and ``flips`` (the bits, in order).
+    With ``weights`` (IPv4 only; uploaded once beside the tuples,
+    ``rss_key_neighbourhood_weighted_device``) the climb is on per-queue loads.
     """
+    _no_ipv6_weights(ipv6, weights)
     key = [int(b) for b in key]
-    score = neighbourhood or _resident_neighbourhood(tuples, htable, nqueues, ipv6)
+    score = neighbourhood or _resident_neighbourhood(tuples, htable, nqueues, ipv6, weights)
     flips = []
     counts = np.asarray(score(key))
     while True:
@@ -178,9 +216,27 @@ def load_tuples(ips_file, ipv6=False):
     return (pack_frame6 if ipv6 else pack_frame)(pd.read_csv(ips_file))
 
 
+def load_weighted_csv(ips_file, column):
+    """``(tuples, weights)`` of a 4-tuple CSV with a ``column`` of per-flow weights, read
+    through pandas; ``ValueError`` unless the column holds integers in [0, 2^32)."""
+    df = pd.read_csv(ips_file)
+    if column not in df.columns:
+        raise ValueError("%s has no column %r" % (ips_file, column))
+    return pack_frame(df), _native.tuple_weights(df[column].to_numpy(), len(df))
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(prog="rss-keysearch", description=__doc__.splitlines()[0])
-    p.add_argument("--ips-file", metavar="PATH", required=True)
+    source = p.add_mutually_exclusive_group(required=True)
+    source.add_argument("--ips-file", metavar="PATH")
+    source.add_argument("--pcap", metavar="PATH",
+                        help="a capture instead of a CSV: its unique IPv4 flows, each weighted "
+                             "by its packets, so that the printed max_load, chi2 and queues used "
+                             "describe the packet load per queue, not the flow count")
+    p.add_argument("--weight-column", metavar="NAME",
+                   help="CSV column of per-flow weights (packets or bytes: integers in "
+                        "[0, 2^32)); the printed max_load, chi2 and queues used then describe "
+                        "the load per queue, not the flow count")
     p.add_argument("--htable-size", metavar="NUM", type=PositiveInt.parse, required=True)
     p.add_argument("--num-queues", metavar="NUM", type=PositiveInt.parse, required=True)
     p.add_argument("--keys", metavar="NUM", type=PositiveInt.parse, default=1024,
@@ -197,13 +253,33 @@ def main(argv=None):
     p.add_argument("--ipv6", action="store_true",
                    help="the file holds IPv6 flows (36-byte hash input, 320 key bits)")
     args = p.parse_args(argv)
-    tuples = load_tuples(args.ips_file, args.ipv6)
+    if args.refine > 0:
+        # refine keeps its tuples in torch tensors: torch opens the device before the
+        # library's first call does (the other order leaves torch without a device)
+        import torch
+        torch.cuda.init()
+    weights = None
+    if args.ipv6 and (args.pcap or args.weight_column):
+        p.error("--ipv6 cannot be combined with --pcap or --weight-column: weighted key "
+                "search serves IPv4 flows only")
+    if args.pcap and args.weight_column:
+        p.error("--weight-column names a CSV column: not allowed with --pcap")
+    if args.pcap:
+        from rss_simulator_nvidia_amd.pcap import read_flows
+        tuples, _, _, weights = read_flows(args.pcap, packet_counts=True)
+    elif args.weight_column:
+        try:
+            tuples, weights = load_weighted_csv(args.ips_file, args.weight_column)
+        except ValueError as err:
+            p.error("--weight-column %s: %s" % (args.weight_column, err))
+    else:
+        tuples = load_tuples(args.ips_file, args.ipv6)
     extra = [args.key] if args.key else []
     ranked = search(tuples, args.htable_size, args.num_queues, args.keys, args.seed, args.top,
-                    extra, args.ipv6)
+                    extra, args.ipv6, weights)
     if args.key:
         base = balance(evaluate([args.key], tuples, args.htable_size, args.num_queues,
-                                ipv6=args.ipv6),
+                                ipv6=args.ipv6, weights=weights),
                        args.htable_size, args.num_queues)
         print("given key: max_load %.4f chi2 %.2f queues used %d"
               % (base["max_load"][0], base["chi2"][0], base["used"][0]))
@@ -212,7 +288,8 @@ def main(argv=None):
               % (key_text(r["key"]), r["max_load"], r["chi2"], r["used"]))
     if args.refine > 0:
         starts = [ranked[0]["key"]] + extra
-        score = _resident_neighbourhood(tuples, args.htable_size, args.num_queues, args.ipv6)
+        score = _resident_neighbourhood(tuples, args.htable_size, args.num_queues, args.ipv6,
+                                        weights)
         refined = [refine(k, tuples, args.htable_size, args.num_queues, args.refine, score)
                    for k in starts]
         refined.sort(key=lambda r: (r["max_load"], r["chi2"]))

@@ -30,9 +30,12 @@ def parse_l4(spec):
         raise ValueError("L4 protocols must be a comma list of tcp, udp, sctp (or none)")
 
 
-def read_flows(path, l4=None, unique=True, ipv6=False):
+def read_flows(path, l4=None, unique=True, ipv6=False, packet_counts=False):
     """Packed tuples of a capture's IPv4 packets (``TUPLE_DTYPE``), or with ``ipv6`` of its
-    IPv6 packets (``TUPLE6_DTYPE``) -> (tuples, protocols, skipped packets)."""
+    IPv6 packets (``TUPLE6_DTYPE``) -> (tuples, protocols, skipped packets).  With
+    ``packet_counts`` a fourth item: uint32 packets per returned tuple (the weights of
+    ``keysearch``'s load ranking) -- each unique flow's packets in the same first-seen order,
+    or ones without ``unique``."""
     try:
         data = np.fromfile(path, dtype=np.uint8)
     except OSError as err:
@@ -45,11 +48,15 @@ def read_flows(path, l4=None, unique=True, ipv6=False):
     if keep != set(PROTOCOLS.values()):
         tuples = tuples.copy()
         tuples["ports"][~np.isin(protos, list(keep))] = 0
+    packets = np.ones(len(tuples), dtype=np.uint32)
     if unique and len(tuples):
         raw = np.ascontiguousarray(tuples).view(np.dtype((np.void, tuples.dtype.itemsize)))
-        _, first = np.unique(raw, return_index=True)
-        order = np.sort(first)
-        tuples, protos = tuples[order], protos[order]
+        _, first, per_flow = np.unique(raw, return_index=True, return_counts=True)
+        by_first = np.argsort(first, kind="stable")  # np.unique sorts by value: back to first seen
+        order = first[by_first]
+        tuples, protos, packets = tuples[order], protos[order], per_flow[by_first].astype(np.uint32)
+    if packet_counts:
+        return tuples, protos, skipped, packets
     return tuples, protos, skipped
 
 

@@ -12,7 +12,15 @@ between device events, the two alternating, every window's time per launch repor
 launch over K keys against K back-to-back counts-only rss_hash6_device launches (all there was
 before it), and one rss_key_neighbourhood6_device launch against one rss_key_search6_device
 launch over the 320 host-prepared flipped keys and against 320 rss_hash6_device launches; the
-contenders alternate, `rounds` windows each, medians reported."""
+contenders alternate, `rounds` windows each, medians reported.
+       python tools/keysearch_bench.py --weighted [n] [H] [Q] [K]
+--weighted times key search by load on n resident uniform tuples: rss_key_search_weighted_device
+over K keys and rss_key_neighbourhood_weighted_device, each with heavy-tailed weights (Zipf 1.3,
+clipped to u32) and with all-ones weights, against the unweighted entries at the same shape in
+the same process (alternating windows, medians), and against the host loop they replace: one
+rss_hash_device launch per key, its queue column copied back and np.bincount(weights=) on the
+host, timed over 16 keys and scaled to K.  One shape per invocation, so that a job gives each
+shape a time limit of its own."""
 import json
 import os
 import sys
@@ -91,6 +99,95 @@ def ipv6_main(argv):
         out["speedup_vs_search6"] = med["search6"] / best
     print(json.dumps(out))
 
+
+def weighted_main(argv):
+    """--weighted [n] [H] [Q] [K]: see the module docstring."""
+    import time
+    n, H, Q, K = ([int(a) for a in argv] + [1 << 20, 128, 24, 1024][len(argv):])[:4]
+    dev = torch.device("cuda:0")
+    s = torch.cuda.current_stream(dev).cuda_stream
+    base_key = keysearch.random_keys(1, seed=7)[0]
+    base = _native.prepare_key(base_key)
+    prepared = [_native.prepare_key(k) for k in keysearch.random_keys(K, seed=0)]
+    win = np.stack([np.ctypeslib.as_array(k.window) for k in prepared]).astype(np.uint32)
+    windows = torch.from_numpy(win.view(np.int32)).to(dev)
+    tuples = torch.empty(3 * n, dtype=torch.int32, device=dev)
+    _native.generate_device(1, 0, n, tuples.data_ptr(), s)
+    rng = np.random.default_rng(3)
+    host_w = {"zipf": np.minimum(rng.zipf(1.3, n), 0xFFFFFFFF).astype(np.uint32),
+              "ones": np.ones(n, dtype=np.uint32)}
+    d_w = {name: torch.from_numpy(w.view(np.int32)).to(dev) for name, w in host_w.items()}
+    width = _native.queue_modulus(H, Q)[1]
+    out = {name: torch.empty((rows, width), dtype=torch.int64, device=dev)
+           for name, rows in (("search", K), ("search_zipf", K), ("search_ones", K),
+                              ("neighbourhood", 128), ("neighbourhood_zipf", 128),
+                              ("neighbourhood_ones", 128))}
+    contenders = {
+        "search": (lambda: _native.key_search_device(
+            windows.data_ptr(), K, tuples.data_ptr(), n, H, Q, out["search"].data_ptr(), s), 100),
+        "neighbourhood": (lambda: _native.key_neighbourhood_device(
+            base, tuples.data_ptr(), n, H, Q, out["neighbourhood"].data_ptr(), s), 500)}
+    for name in host_w:
+        contenders["search_" + name] = (lambda name=name: _native.key_search_weighted_device(
+            windows.data_ptr(), K, tuples.data_ptr(), d_w[name].data_ptr(), n, H, Q,
+            out["search_" + name].data_ptr(), s), 100)
+        contenders["neighbourhood_" + name] = (
+            lambda name=name: _native.key_neighbourhood_weighted_device(
+                base, tuples.data_ptr(), d_w[name].data_ptr(), n, H, Q,
+                out["neighbourhood_" + name].data_ptr(), s), 500)
+    for fn, _ in contenders.values():  # warm every shape, then check before timing
+        for _ in range(10):
+            fn()
+    torch.cuda.synchronize()
+    total = int(host_w["zipf"].sum(dtype=np.uint64))
+    for kind in ("search", "neighbourhood"):
+        assert torch.equal(out[kind + "_ones"], out[kind])
+        assert bool((out[kind + "_zipf"].sum(dim=1) == total).all())
+
+    # the host loop the weighted search replaces, over 16 keys
+    queues = torch.empty(n, dtype=torch.int32, device=dev)
+    loop_keys = 16
+    weights64 = host_w["zipf"].astype(np.float64)  # sums < 2^53: exact
+    loop_loads = np.zeros((loop_keys, width))
+
+    def host_loop():
+        for k in range(loop_keys):
+            _native.hash_device(prepared[k], tuples.data_ptr(), n, H, Q, None, queues.data_ptr(),
+                                None, 0, s)
+            loop_loads[k] = np.bincount(queues.cpu().numpy(), weights=weights64, minlength=width)
+
+    host_loop()  # warm
+    assert np.array_equal(loop_loads.astype(np.uint64),
+                          out["search_zipf"][:loop_keys].cpu().numpy().view(np.uint64))
+    loop_ms = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        host_loop()
+        loop_ms.append((time.perf_counter() - t0) * 1e3 * K / loop_keys)
+
+    rounds = 7
+    times = {name: [] for name in contenders}
+    for _ in range(rounds):
+        for name, (fn, reps) in contenders.items():
+            times[name].append(window_ms(fn, reps))
+    med = {name: float(np.median(v)) for name, v in times.items()}
+    print(json.dumps({
+        "mode": "weighted", "keys": K, "flows": n, "htable": H, "queues": Q,
+        "reps_per_window": {name: reps for name, (_, reps) in contenders.items()},
+        "window_ms": times, "median_ms": med,
+        "host_loop_ms_scaled_to_keys": loop_ms, "host_loop_keys_timed": loop_keys,
+        "host_loop_median_ms": float(np.median(loop_ms)),
+        "search_weighted_over_unweighted": {k: med["search_" + k] / med["search"] for k in host_w},
+        "neighbourhood_weighted_over_unweighted": {
+            k: med["neighbourhood_" + k] / med["neighbourhood"] for k in host_w},
+        "host_loop_over_search_weighted": float(np.median(loop_ms)) / med["search_zipf"],
+        "search_weighted_key_flow_evals_per_s": K * n / (med["search_zipf"] / 1e3),
+        "neighbourhood_weighted_key_flow_evals_per_s": 128 * n / (med["neighbourhood_zipf"] / 1e3)}))
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "--weighted":
+    weighted_main(sys.argv[2:])
+    sys.exit(0)
 
 if len(sys.argv) > 1 and sys.argv[1] == "--ipv6":
     ipv6_main(sys.argv[2:])
