@@ -269,6 +269,48 @@ int rss_key_neighbourhood_weighted_device(const rss_key* key, const rss_tuple4* 
                                           uint32_t nqueues, uint64_t* d_loads, void* stream);
 
 /*
+ * Symmetric RSS: rank the keys that hash both directions of a connection to one queue.  A key
+ * with a 16-bit period (DPDK's 6d:5a:6d:5a:... is pattern 0x6d5a) has window[i] depending only
+ * on i % 16, so a tuple's hash depends only on f, the XOR of its 16-bit half-words: with f_r =
+ * bit 15 - r of f and p the pattern, g = XOR over r with f_r set of rotl16(p, r) and hash =
+ * (g << 16) | g.  Any flow set -- IPv4 or IPv6, weighted or not -- therefore collapses into a
+ * histogram of RSS_SYMMETRIC_PATTERNS fold values, and all 65536 patterns are scored from it
+ * in 2^32 (fold, pattern) evaluations whatever n is.
+ *
+ * rss_symmetric_key: key[i] = pattern >> 8 (i even) or pattern & 0xFF (i odd) -- the literal
+ * key to program; len even, RSS_KEY_MIN_BYTES..RSS_KEY_MAX_BYTES.
+ * rss_symmetric_fold_device: d_tuples n tuples of `words` host-order words (3: rss_tuple4, 9:
+ * rss_tuple6); `fields` a set of RSS_FIELD_* bits (1..15; every field is a multiple of 16 bits,
+ * so leaving one out only masks its half-words); d_weights n uint32 or NULL (every weight 1);
+ * d_folds RSS_SYMMETRIC_PATTERNS uint64: d_folds[f] = the sum of the weights of the tuples
+ * that fold to f, overwritten unless flags has RSS_FLAG_ACCUMULATE (the only flag honoured), so
+ * that batches -- and an IPv4 and an IPv6 capture -- can be summed.  Exact for any u32 weights
+ * and any n.  Tuples and weights both 16-byte aligned take the 4-tuples-per-lane path.
+ * rss_symmetric_search_device: d_loads npatterns x nqueues uint64, row r = pattern
+ * first_pattern + r, overwritten: d_loads[r][q] = the sum of d_folds[f] over the f with
+ * ((g(f, p) * 0x10001) % htable) % nqueues == q -- the loads under rss_symmetric_key(p).
+ * Exact for any htable, nqueues >= 1: lane-private 64-bit LDS bins for 8 patterns per
+ * workgroup up to 79 queues (power-of-two htable <= 256), for 4 up to 159, shared bins up to
+ * 5088, global 64-bit atomics past them.  Columns [min(htable, nqueues), nqueues) are zero.
+ * Both device entries are stream-ordered and clear their output by a kernel of the same call
+ * (n == 0 only clears), so they can be captured into a graph.
+ * rss_symmetric_search_host: the fold and the scan on host buffers under the context's lock,
+ * as rss_key_search_host; synchronous; n == 0 zeroes h_loads on the host.
+ * RSS_EINVAL, before any device work, with rss_last_error naming the entry and the cause: a
+ * NULL folds, loads or ctx pointer; n > 0 with NULL tuples; words not 3 or 9; fields 0 or > 15;
+ * npatterns == 0 or first_pattern + npatterns > 65536; htable or nqueues 0; for
+ * rss_symmetric_key a NULL key or an odd or out-of-range len.
+ */
+#define RSS_SYMMETRIC_PATTERNS 65536u   /* also the number of fold values */
+int rss_symmetric_key(uint16_t pattern, uint8_t* key, size_t len);
+int rss_symmetric_fold_device(const void* d_tuples, uint32_t words, uint32_t fields,
+                              const uint32_t* d_weights, size_t n, uint64_t* d_folds,
+                              uint32_t flags, void* stream);
+int rss_symmetric_search_device(const uint64_t* d_folds, uint32_t first_pattern,
+                                uint32_t npatterns, uint32_t htable, uint32_t nqueues,
+                                uint64_t* d_loads, void* stream);
+
+/*
  * IPv6.  36-byte input = src addr (16 B) | dst addr (16 B) |
  * src port | dst port, the layout of the Microsoft RSS IPv6 hash; stored as nine
  * host-order words whose big-endian bytes are that input (w[0..3] src, w[4..7]
@@ -527,6 +569,14 @@ int rss_key_neighbourhood_weighted_host(rss_ctx* ctx, const rss_key* key,
                                         const rss_tuple4* h_tuples, const uint32_t* h_weights,
                                         size_t n, uint32_t htable, uint32_t nqueues,
                                         uint64_t* h_loads);
+
+/* rss_symmetric_fold_device + rss_symmetric_search_device on host buffers (described with
+ * them): h_tuples n x `words` uint32, h_weights n uint32 or NULL, h_loads npatterns x nqueues
+ * uint64.  Synchronous. */
+int rss_symmetric_search_host(rss_ctx* ctx, const void* h_tuples, uint32_t words, uint32_t fields,
+                              const uint32_t* h_weights, size_t n, uint32_t first_pattern,
+                              uint32_t npatterns, uint32_t htable, uint32_t nqueues,
+                              uint64_t* h_loads);
 
 /* rss_key_search6_device on host buffers (keys: nkeys prepared rss_key6; h_counts: nkeys x
  * nqueues uint64), as rss_key_search_host.  Synchronous.  Refuses what the device entry

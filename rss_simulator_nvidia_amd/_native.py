@@ -44,7 +44,10 @@ EXPORTED_SYMBOLS = (
     "rss_key_neighbourhood6_device", "rss_key_neighbourhood6_host",
     "rss_key_search_weighted_device", "rss_key_neighbourhood_weighted_device",
     "rss_key_search_weighted_host", "rss_key_neighbourhood_weighted_host",
+    "rss_symmetric_key", "rss_symmetric_fold_device", "rss_symmetric_search_device",
+    "rss_symmetric_search_host",
 )
+SYMMETRIC_PATTERNS = 65536  # RSS_SYMMETRIC_PATTERNS: 16-bit key patterns = fold values
 KEY_NEIGHBOURS = 128  # RSS_KEY_NEIGHBOURS: the key bits an IPv4 hash reads
 KEY6_NEIGHBOURS = 320  # RSS_KEY6_NEIGHBOURS: the key bits an IPv6 hash reads
 FIELD_SRC_IP, FIELD_DST_IP, FIELD_SRC_PORT, FIELD_DST_PORT = 1, 2, 4, 8
@@ -117,6 +120,11 @@ def _bind(lib):
         "rss_key_search_weighted_host": ([vp, vp, sz, vp, vp, sz, u32, u32, vp], ctypes.c_int),
         "rss_key_neighbourhood_weighted_host": ([vp, key_p, vp, vp, sz, u32, u32, vp],
                                                 ctypes.c_int),
+        "rss_symmetric_key": ([ctypes.c_uint16, vp, sz], ctypes.c_int),
+        "rss_symmetric_fold_device": ([vp, u32, u32, vp, sz, vp, u32, vp], ctypes.c_int),
+        "rss_symmetric_search_device": ([vp, u32, u32, u32, u32, vp, vp], ctypes.c_int),
+        "rss_symmetric_search_host": ([vp, vp, u32, u32, vp, sz, u32, u32, u32, u32, vp],
+                                      ctypes.c_int),
         "rss_key_search6_device": ([vp, sz, vp, sz, u32, u32, vp, vp], ctypes.c_int),
         "rss_key_search6_host": ([vp, vp, sz, vp, sz, u32, u32, vp], ctypes.c_int),
         "rss_key_neighbourhood6_device": ([ctypes.POINTER(RssKey6), vp, sz, u32, u32, vp, vp],
@@ -584,6 +592,37 @@ class HostContext:
         return out
 
 
+    def symmetric_search(self, tuples, htable, nqueues, first_pattern=0,
+                         npatterns=SYMMETRIC_PATTERNS, ipv6=False, weights=None,
+                         fields=FIELDS_ALL):
+        """Per-queue loads (uint64[npatterns, min(htable, nqueues)]) of ``tuples`` under the
+        symmetric keys of patterns ``first_pattern ..`` (``rss_symmetric_search_host``):
+        IPv4 or (``ipv6``) IPv6 tuples, optional u32 ``weights``, ``fields`` a mask or 'sdfn'
+        letters."""
+        htable, nqueues = queue_modulus(htable, nqueues)
+        arr = _tuples6(tuples) if ipv6 else np.ascontiguousarray(tuples)
+        if not ipv6 and arr.dtype != TUPLE_DTYPE:
+            arr = np.ascontiguousarray(arr, dtype=np.uint32).reshape(-1, 3)
+        w = tuple_weights(weights, len(arr)) if weights is not None else None
+        if isinstance(fields, str):
+            fields = parse_fields(fields)
+        out = np.zeros((max(int(npatterns), 0), nqueues), dtype=np.uint64)
+        _check(self._lib.rss_symmetric_search_host(
+            self._ctx, arr.ctypes.data, 9 if ipv6 else 3, fields, ptr(w), len(arr), first_pattern,
+            npatterns, htable, nqueues, out.ctypes.data), "rss_symmetric_search_host")
+        return out
+
+
+def symmetric_key(pattern, length=40):
+    """The ``length`` bytes of the symmetric key of 16-bit ``pattern`` (``rss_symmetric_key``):
+    ``pattern >> 8, pattern & 0xFF`` repeated."""
+    if not 0 <= int(pattern) < SYMMETRIC_PATTERNS:
+        raise ValueError("pattern must lie in [0, 65536), got %r" % (pattern,))
+    buf = (ctypes.c_uint8 * max(int(length), 1))()
+    _check(load().rss_symmetric_key(int(pattern), buf, int(length)), "rss_symmetric_key")
+    return list(buf)
+
+
 def tuple_weights(weights, n):
     """``weights`` as contiguous uint32[n] for the weighted key-search entries: one integer in
     [0, 2^32) per tuple, anything else is a ``ValueError``."""
@@ -799,6 +838,23 @@ def key_neighbourhood_weighted_device(key, tuples_ptr, weights_ptr, n, htable, n
     _check(load().rss_key_neighbourhood_weighted_device(ctypes.byref(key), tuples_ptr, weights_ptr,
                                                         n, htable, nqueues, loads_ptr, stream),
            "rss_key_neighbourhood_weighted_device")
+
+
+def symmetric_fold_device(tuples_ptr, words, fields, weights_ptr, n, folds_ptr, flags=0,
+                          stream=None):
+    """Stream-ordered ``rss_symmetric_fold_device`` on raw device pointers (ints): ``words`` 3
+    or 9 per tuple, ``weights_ptr`` n uint32 or None, ``folds_ptr`` uint64[65536]."""
+    _check(load().rss_symmetric_fold_device(tuples_ptr, words, fields, weights_ptr, n, folds_ptr,
+                                            flags, stream), "rss_symmetric_fold_device")
+
+
+def symmetric_search_device(folds_ptr, first_pattern, npatterns, htable, nqueues, loads_ptr,
+                            stream=None):
+    """Stream-ordered ``rss_symmetric_search_device`` on raw device pointers (ints);
+    ``loads_ptr``: uint64[npatterns, min(htable, nqueues)], overwritten."""
+    htable, nqueues = queue_modulus(htable, nqueues)
+    _check(load().rss_symmetric_search_device(folds_ptr, first_pattern, npatterns, htable, nqueues,
+                                              loads_ptr, stream), "rss_symmetric_search_device")
 
 
 def key_search6_device(windows_ptr, nkeys, tuples_ptr, n, htable, nqueues, counts_ptr,

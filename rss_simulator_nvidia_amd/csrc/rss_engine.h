@@ -1,5 +1,5 @@
 // rss_engine.h -- the engine's launchers (rss_toeplitz.hip, rss_keysearch.hip,
-// rss_keysearch6.hip, rss_neighbourhood.hip, rss_keysearch_weighted.hip) as the C ABI (rss_host.hip) calls
+// rss_keysearch6.hip, rss_neighbourhood.hip, rss_keysearch_weighted.hip, rss_symmetric.hip) as the C ABI (rss_host.hip) calls
 // them, and the HIP error macro both use.  Internal, not ABI.
 #pragma once
 
@@ -58,6 +58,14 @@ RSS_HIDDEN int launch_neighbourhood_weighted(const rss_key* key, const rss_tuple
                                              const uint32_t* d_weights, size_t n, uint32_t htable,
                                              uint32_t nqueues, uint64_t* d_loads,
                                              hipStream_t stream);
+// rss_symmetric_fold_device / rss_symmetric_search_device (rss_symmetric.hip; arguments
+// validated by the caller)
+RSS_HIDDEN int launch_symmetric_fold(const void* d_tuples, uint32_t words, uint32_t fields,
+                                     const uint32_t* d_weights, size_t n, uint64_t* d_folds,
+                                     uint32_t flags, hipStream_t stream);
+RSS_HIDDEN int launch_symmetric_search(const uint64_t* d_folds, uint32_t first_pattern,
+                                       uint32_t npatterns, uint32_t htable, uint32_t nqueues,
+                                       uint64_t* d_loads, hipStream_t stream);
 // d_counts[0, cells) = 0 by a kernel (rss_neighbourhood.hip): capturable, unlike a memset node
 RSS_HIDDEN int launch_zero_counts(uint64_t* d_counts, uint64_t cells, hipStream_t stream);
 // rss_generate_tuples (n > 0, d_tuples non-NULL)

@@ -130,14 +130,41 @@ int check_weights(const char* who, const uint32_t* weights, size_t n) {
     return RSS_OK;
 }
 
+// rss_symmetric_fold_device / rss_symmetric_search_host: the flow set
+int check_symmetric_fold(const char* who, const void* tuples, uint32_t words, uint32_t fields,
+                         size_t n) {
+    if (n && !tuples) return rss_set_error(RSS_EINVAL, "%s: tuples is NULL", who);
+    if (words != 3 && words != 9)
+        return rss_set_error(RSS_EINVAL, "%s: words must be 3 (IPv4) or 9 (IPv6), got %u", who,
+                             words);
+    if (fields == 0 || (fields & ~RSS_FIELDS_ALL))
+        return rss_set_error(RSS_EINVAL, "%s: bad field mask 0x%x", who, fields);
+    return RSS_OK;
+}
+
+// rss_symmetric_search_device / _host: the pattern range and the table
+int check_symmetric_search(const char* who, uint32_t first_pattern, uint32_t npatterns,
+                           uint32_t htable, uint32_t nqueues) {
+    if (npatterns == 0) return rss_set_error(RSS_EINVAL, "%s: no patterns", who);
+    if ((uint64_t)first_pattern + npatterns > RSS_SYMMETRIC_PATTERNS)
+        return rss_set_error(RSS_EINVAL, "%s: patterns [%u, %llu) exceed %u", who, first_pattern,
+                             (unsigned long long)first_pattern + npatterns,
+                             RSS_SYMMETRIC_PATTERNS);
+    if (htable < 1 || nqueues < 1)
+        return rss_set_error(RSS_EINVAL, "%s: htable (%u) and nqueues (%u) must be >= 1", who,
+                             htable, nqueues);
+    return RSS_OK;
+}
+
 // The key-search host entries (IPv4 / IPv6, search / neighbourhood, weighted or not): under the
 // context's lock upload `windows` (search only; empty otherwise), the tuples and their weights
 // (weighted only; NULL otherwise), `launch(d_windows, d_tuples, d_weights, d_counts, stream)`,
-// copy count_bytes of counts back.  Synchronous.
+// copy count_bytes of counts back.  `scratch_bytes` more device bytes follow the counts (the
+// symmetric search's folds).  Synchronous.
 template <typename Tuple, typename Launch>
 int key_host_run(const char* who, rss_ctx* ctx, const std::vector<uint32_t>& windows,
                  const Tuple* h_tuples, size_t n, size_t count_bytes, uint64_t* h_counts,
-                 Launch launch, const uint32_t* h_weights = nullptr) {
+                 Launch launch, const uint32_t* h_weights = nullptr, size_t scratch_bytes = 0) {
     std::lock_guard<std::mutex> lock(ctx->mu);  // (struct rss_ctx)
     RSS_HIP_CHECK(hipSetDevice(ctx->device));
     uint32_t* d_w = nullptr;
@@ -157,7 +184,7 @@ int key_host_run(const char* who, rss_ctx* ctx, const std::vector<uint32_t>& win
     if (window_bytes) e = hipMalloc(&d_w, window_bytes);
     if (e == hipSuccess && n) e = hipMalloc(&d_t, n * sizeof(Tuple));
     if (e == hipSuccess && n && h_weights) e = hipMalloc(&d_wt, n * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&d_c, count_bytes);
+    if (e == hipSuccess) e = hipMalloc(&d_c, count_bytes + scratch_bytes);
     if (e == hipSuccess && window_bytes)
         e = hipMemcpyAsync(d_w, windows.data(), window_bytes, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && n)
@@ -379,6 +406,37 @@ int rss_key_neighbourhood_weighted_device(const rss_key* key, const rss_tuple4* 
     if (rc) return rc;
     return rss::launch_neighbourhood_weighted(key, d_tuples, d_weights, n, htable, nqueues, d_loads,
                                               static_cast<hipStream_t>(stream));
+}
+
+int rss_symmetric_key(uint16_t pattern, uint8_t* key, size_t len) {
+    if (!key) return rss_set_error(RSS_EINVAL, "rss_symmetric_key: key is NULL");
+    if (len % 2 || len < RSS_KEY_MIN_BYTES || len > RSS_KEY_MAX_BYTES)
+        return rss_set_error(RSS_EINVAL, "rss_symmetric_key: len must be even and in [%d, %d], got %zu",
+                             RSS_KEY_MIN_BYTES, RSS_KEY_MAX_BYTES, len);
+    for (size_t i = 0; i < len; ++i) key[i] = (uint8_t)(i % 2 ? pattern & 0xFF : pattern >> 8);
+    return RSS_OK;
+}
+
+int rss_symmetric_fold_device(const void* d_tuples, uint32_t words, uint32_t fields,
+                              const uint32_t* d_weights, size_t n, uint64_t* d_folds,
+                              uint32_t flags, void* stream) {
+    const char* who = "rss_symmetric_fold_device";
+    if (!d_folds) return rss_set_error(RSS_EINVAL, "%s: folds is NULL", who);
+    int rc = check_symmetric_fold(who, d_tuples, words, fields, n);
+    if (rc) return rc;
+    return rss::launch_symmetric_fold(d_tuples, words, fields, d_weights, n, d_folds, flags,
+                                      static_cast<hipStream_t>(stream));
+}
+
+int rss_symmetric_search_device(const uint64_t* d_folds, uint32_t first_pattern,
+                                uint32_t npatterns, uint32_t htable, uint32_t nqueues,
+                                uint64_t* d_loads, void* stream) {
+    const char* who = "rss_symmetric_search_device";
+    if (!d_folds || !d_loads) return rss_set_error(RSS_EINVAL, "%s: folds or loads is NULL", who);
+    int rc = check_symmetric_search(who, first_pattern, npatterns, htable, nqueues);
+    if (rc) return rc;
+    return rss::launch_symmetric_search(d_folds, first_pattern, npatterns, htable, nqueues, d_loads,
+                                        static_cast<hipStream_t>(stream));
 }
 
 int rss_generate_tuples(uint64_t seed, uint64_t first_index, size_t n, rss_tuple4* d_tuples,
@@ -872,6 +930,37 @@ int rss_key_neighbourhood_weighted_host(rss_ctx* ctx, const rss_key* key,
                             return rss::launch_neighbourhood_weighted(key, d_t, d_wt, n, htable,
                                                                       nqueues, d_c, s);
                         }, h_weights);
+}
+
+int rss_symmetric_search_host(rss_ctx* ctx, const void* h_tuples, uint32_t words, uint32_t fields,
+                              const uint32_t* h_weights, size_t n, uint32_t first_pattern,
+                              uint32_t npatterns, uint32_t htable, uint32_t nqueues,
+                              uint64_t* h_loads) {
+    const char* who = "rss_symmetric_search_host";
+    if (!ctx) return rss_set_error(RSS_EINVAL, "%s: context is NULL", who);
+    if (!h_loads) return rss_set_error(RSS_EINVAL, "%s: loads is NULL", who);
+    int rc = check_symmetric_fold(who, h_tuples, words, fields, n);
+    if (rc == RSS_OK) rc = check_symmetric_search(who, first_pattern, npatterns, htable, nqueues);
+    if (rc) return rc;
+    const size_t load_bytes = sizeof(uint64_t) * npatterns * nqueues;
+    if (n == 0) {
+        memset(h_loads, 0, load_bytes);
+        return RSS_OK;
+    }
+    // the folds live behind the loads in one allocation
+    auto launch = [&](uint32_t*, auto* d_t, uint32_t* d_wt, uint64_t* d_c, hipStream_t s) {
+        uint64_t* d_folds = d_c + (size_t)npatterns * nqueues;
+        int r = rss::launch_symmetric_fold(d_t, words, fields, d_wt, n, d_folds, 0, s);
+        if (r) return r;
+        return rss::launch_symmetric_search(d_folds, first_pattern, npatterns, htable, nqueues, d_c,
+                                            s);
+    };
+    const size_t fold_bytes = sizeof(uint64_t) * RSS_SYMMETRIC_PATTERNS;
+    if (words == 3)
+        return key_host_run(who, ctx, {}, static_cast<const rss_tuple4*>(h_tuples), n, load_bytes,
+                            h_loads, launch, h_weights, fold_bytes);
+    return key_host_run(who, ctx, {}, static_cast<const rss_tuple6*>(h_tuples), n, load_bytes,
+                        h_loads, launch, h_weights, fold_bytes);
 }
 
 int rss_key_search6_host(rss_ctx* ctx, const rss_key6* keys, size_t nkeys,

@@ -1,8 +1,8 @@
 // rss_keysearch_tables.h -- what the key-search kernel files share beyond rss_kernel_common.h
 // (internal, not ABI): the 8-byte table sets of the search kernels (packed small tables, wide
 // pair tables; described in rss_keysearch.hip), the neighbourhood's per-tuple flip span
-// (rss_neighbourhood.hip) and the two launch-grid rules.  Used by rss_keysearch.hip,
-// rss_neighbourhood.hip and rss_keysearch_weighted.hip; anonymous namespace, as
+// (rss_neighbourhood.hip), the u64 load rows and the two launch-grid rules.  Used by rss_keysearch.hip,
+// rss_neighbourhood.hip, rss_keysearch_weighted.hip and rss_symmetric.hip; anonymous namespace, as
 // rss_kernel_common.h.
 #pragma once
 
@@ -148,6 +148,18 @@ __device__ __forceinline__ uint2 toeplitz_hash_pair(const uint2* __restrict__ lu
     const uint2 a = small_pair_word<0>(base, w0), b = small_pair_word<7>(base, w1);
     const uint2 c = small_pair_word<14>(base, w2);
     return make_uint2(xor3(a.x, b.x, c.x), xor3(a.y, b.y, c.y));
+}
+
+// ----------------------------------------------------- u64 load bins (weighted, symmetric) --
+using u64 = unsigned long long;
+constexpr uint32_t kLoadRowBytes = kBinCols * 8;  // one (queue, key)'s columns: the 64 banks once
+static_assert(kLoadRowBytes == 256, "a row of u64 columns covers the LDS banks exactly once");
+
+// sum of row e's 32 lane columns (rows of 32 u64 from `bins`), started at column e
+__device__ __forceinline__ u64 row_sum(const u64* bins, uint32_t e) {
+    u64 s = 0;
+    for (uint32_t c = 0; c < kBinCols; ++c) s += bins[e * kBinCols + ((c + e) & (kBinCols - 1))];
+    return s;
 }
 
 // search kernels' workgroups along x: ~256K tuples per workgroup amortise its 120 KiB table build

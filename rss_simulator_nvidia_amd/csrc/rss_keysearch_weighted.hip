@@ -49,11 +49,7 @@
 
 namespace {
 
-using u64 = unsigned long long;
 using WeightedKernelFn = void (*)(const LaunchParams, const uint32_t*);
-
-constexpr uint32_t kLoadRowBytes = kBinCols * 8;  // one (queue, key)'s columns: the 64 banks once
-static_assert(kLoadRowBytes == 256, "a row of u64 columns covers the LDS banks exactly once");
 
 __device__ __forceinline__ void lds_add_load(u64* bin, uint32_t weight) {  // ds_add_u64
     __hip_atomic_fetch_add(bin, (u64)weight, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -86,13 +82,6 @@ __device__ __forceinline__ void walk_weighted(const LaunchParams& p,
         const uint32_t* t = reinterpret_cast<const uint32_t*>(p.tuples) + 3 * i;
         count(t[0], t[1], t[2], weights[i]);
     }
-}
-
-// sum of row e's 32 lane columns (rows of 32 u64 from `bins`), started at column e
-__device__ __forceinline__ u64 row_sum(const u64* bins, uint32_t e) {
-    u64 s = 0;
-    for (uint32_t c = 0; c < kBinCols; ++c) s += bins[e * kBinCols + ((c + e) & (kBinCols - 1))];
-    return s;
 }
 
 // ------------------------------------------------------------ search, packed tables --

@@ -23,6 +23,13 @@ flips the best bit until none improves the spread.
 capture: its unique flows, weighted by their packets) rank and refine by the **load** each
 key puts on a queue instead of the number of flows (``rss_key_search_weighted_device``,
 ``rss_key_neighbourhood_weighted_device``; IPv4 flows).
+
+``--symmetric`` ranks the 65536 symmetric keys instead -- a 16-bit pattern repeated over the
+key (DPDK's ``6d:5a:6d:5a:...``), which sends both directions of a connection to one queue.
+Their hash depends only on the XOR of a tuple's 16-bit half-words, so the flows are folded
+into a 65536-bin histogram once (``rss_symmetric_fold_device``) and every pattern is scored
+from it (``rss_symmetric_search_device``): exhaustive and exact, for IPv4 or IPv6 flows,
+weighted or not.
 """
 import argparse
 import random
@@ -115,6 +122,60 @@ def search(tuples, htable, nqueues, n_keys=1024, seed=0, top=10, extra_keys=(), 
     order = np.lexsort((m["chi2"], m["max_load"]))
     return [{"key": keys[i], "max_load": float(m["max_load"][i]), "chi2": float(m["chi2"][i]),
              "used": int(m["used"][i]), "counts": counts[i]} for i in order[:top]]
+
+
+def symmetric_key(pattern, length=HASH_KEY_BYTES_LENGTH):
+    """The symmetric key of 16-bit ``pattern``: ``pattern >> 8, pattern & 0xFF`` repeated over
+    ``length`` bytes (``symmetric_key(0x6d5a)`` is DPDK's ``6d:5a:6d:5a:...``)."""
+    return _native.symmetric_key(pattern, length)
+
+
+SYMMETRIC_CHUNK_BYTES = 256 << 20  # one scan's loads in symmetric_search
+
+
+def _pattern_range(patterns):
+    if patterns is None:
+        return 0, _native.SYMMETRIC_PATTERNS
+    if isinstance(patterns, range):
+        if patterns.step != 1:
+            raise ValueError("patterns must be consecutive, got %r" % (patterns,))
+        return patterns.start, len(patterns)
+    first, count = patterns
+    return int(first), int(count)
+
+
+def symmetric_loads(tuples, htable, nqueues, patterns=None, ipv6=False, weights=None,
+                    fields=_native.FIELDS_ALL, ctx=None):
+    """uint64 loads ``[npatterns, min(H, Q)]`` of packed ``tuples`` under the symmetric keys of
+    ``patterns`` (a ``range`` or ``(first, count)``; default all 65536): row r is the per-queue
+    flow counts -- with ``weights`` (one u32 per tuple) the loads -- under
+    ``symmetric_key(first + r)`` (GPU: one fold of the flows, one scan of the patterns).
+    ``ipv6``: ``TUPLE6_DTYPE`` or ``(n, 9)`` uint32 tuples; ``fields``: the hashed fields, a
+    mask or 'sdfn' letters."""
+    first, count = _pattern_range(patterns)
+    ctx = ctx or _native.default_context()
+    return ctx.symmetric_search(tuples, htable, nqueues, first, count, ipv6, weights, fields)
+
+
+def symmetric_search(tuples, htable, nqueues, patterns=None, ipv6=False, weights=None,
+                     fields=_native.FIELDS_ALL, top=10):
+    """Rank the symmetric keys of ``patterns`` (default all 65536) for ``tuples`` with
+    :func:`balance`, exhaustively; the range is scanned in chunks whose loads stay at or below
+    256 MiB.  Returns dicts like :func:`search` (best first) plus ``"pattern"``."""
+    first, count = _pattern_range(patterns)
+    width = _native.queue_modulus(htable, nqueues)[1]
+    chunk = max(1, SYMMETRIC_CHUNK_BYTES // (8 * width))
+    best = []  # (max_load, chi2, pattern, used, counts)
+    for start in range(first, first + count, chunk):
+        loads = symmetric_loads(tuples, htable, nqueues, (start, min(chunk, first + count - start)),
+                                ipv6, weights, fields)
+        m = balance(loads, htable, nqueues)
+        for i in np.lexsort((m["chi2"], m["max_load"]))[:top]:
+            best.append((float(m["max_load"][i]), float(m["chi2"][i]), start + int(i),
+                         int(m["used"][i]), loads[i].copy()))
+        best = sorted(best, key=lambda r: r[:3])[:top]
+    return [{"key": symmetric_key(p), "pattern": p, "max_load": ml, "chi2": chi2, "used": used,
+             "counts": counts} for ml, chi2, p, used, counts in best]
 
 
 def flip_bit(key, j):
@@ -225,6 +286,27 @@ def load_weighted_csv(ips_file, column):
     return pack_frame(df), _native.tuple_weights(df[column].to_numpy(), len(df))
 
 
+def load_weighted_csv6(ips_file, column):
+    """:func:`load_weighted_csv` for a CSV of IPv6 flows (``TUPLE6_DTYPE`` tuples)."""
+    df = pd.read_csv(ips_file)
+    if column not in df.columns:
+        raise ValueError("%s has no column %r" % (ips_file, column))
+    return pack_frame6(df), _native.tuple_weights(df[column].to_numpy(), len(df))
+
+
+def _score_given_symmetric(key, tuples, htable, nqueues, ipv6, weights):
+    """``--symmetric``: the ``--key-file`` key's loads.  The hash entries serve any key, IPv4 or
+    IPv6; weighted, the key is one more candidate of the weighted search (IPv4), and an IPv6
+    key's loads are its queues' weights summed on the host."""
+    if weights is None or not ipv6:
+        return evaluate([key], tuples, htable, nqueues, ipv6=ipv6, weights=weights)
+    from rss_simulator_nvidia_amd.toeplitz import Toeplitz
+    _, queues, counts = Toeplitz(key).compute_queues6(tuples, htable, nqueues)
+    loads = np.zeros(len(counts), dtype=np.uint64)
+    np.add.at(loads, queues, weights.astype(np.uint64))
+    return loads[None, :_native.queue_modulus(htable, nqueues)[1]]
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(prog="rss-keysearch", description=__doc__.splitlines()[0])
     source = p.add_mutually_exclusive_group(required=True)
@@ -240,8 +322,9 @@ def main(argv=None):
     p.add_argument("--htable-size", metavar="NUM", type=PositiveInt.parse, required=True)
     p.add_argument("--num-queues", metavar="NUM", type=PositiveInt.parse, required=True)
     p.add_argument("--keys", metavar="NUM", type=PositiveInt.parse, default=1024,
-                   help="random candidate keys to evaluate")
-    p.add_argument("--seed", type=int, default=0)
+                   help="random candidate keys to evaluate (unused with --symmetric)")
+    p.add_argument("--seed", type=int, default=0, help="of the random candidates (unused with "
+                                                       "--symmetric)")
     p.add_argument("--top", metavar="NUM", type=PositiveInt.parse, default=5)
     p.add_argument("--key-file", metavar="PATH", dest="key",
                    type=apt_decorator(HashKey.from_file),
@@ -252,35 +335,49 @@ def main(argv=None):
     p.add_argument("--out", metavar="PATH", help="write the best key in --key-file format")
     p.add_argument("--ipv6", action="store_true",
                    help="the file holds IPv6 flows (36-byte hash input, 320 key bits)")
+    p.add_argument("--symmetric", action="store_true",
+                   help="rank all 65536 symmetric keys (a 16-bit pattern repeated, like DPDK's "
+                        "6d:5a:...) instead of random candidates: both directions of a "
+                        "connection share a queue; exhaustive, IPv4 or IPv6, weighted or not")
     args = p.parse_args(argv)
+    if args.symmetric and args.refine > 0:
+        p.error("--refine cannot be combined with --symmetric: a single-bit flip breaks the "
+                "key's symmetry")
     if args.refine > 0:
         # refine keeps its tuples in torch tensors: torch opens the device before the
         # library's first call does (the other order leaves torch without a device)
         import torch
         torch.cuda.init()
     weights = None
-    if args.ipv6 and (args.pcap or args.weight_column):
+    if args.ipv6 and (args.pcap or args.weight_column) and not args.symmetric:
         p.error("--ipv6 cannot be combined with --pcap or --weight-column: weighted key "
                 "search serves IPv4 flows only")
     if args.pcap and args.weight_column:
         p.error("--weight-column names a CSV column: not allowed with --pcap")
     if args.pcap:
         from rss_simulator_nvidia_amd.pcap import read_flows
-        tuples, _, _, weights = read_flows(args.pcap, packet_counts=True)
+        tuples, _, _, weights = read_flows(args.pcap, ipv6=args.ipv6, packet_counts=True)
     elif args.weight_column:
         try:
-            tuples, weights = load_weighted_csv(args.ips_file, args.weight_column)
+            tuples, weights = (load_weighted_csv6 if args.ipv6 else load_weighted_csv)(
+                args.ips_file, args.weight_column)
         except ValueError as err:
             p.error("--weight-column %s: %s" % (args.weight_column, err))
     else:
         tuples = load_tuples(args.ips_file, args.ipv6)
     extra = [args.key] if args.key else []
-    ranked = search(tuples, args.htable_size, args.num_queues, args.keys, args.seed, args.top,
-                    extra, args.ipv6, weights)
+    if args.symmetric:
+        ranked = symmetric_search(tuples, args.htable_size, args.num_queues, ipv6=args.ipv6,
+                                  weights=weights, top=args.top)
+    else:
+        ranked = search(tuples, args.htable_size, args.num_queues, args.keys, args.seed, args.top,
+                        extra, args.ipv6, weights)
     if args.key:
-        base = balance(evaluate([args.key], tuples, args.htable_size, args.num_queues,
-                                ipv6=args.ipv6, weights=weights),
-                       args.htable_size, args.num_queues)
+        given = (_score_given_symmetric(args.key, tuples, args.htable_size, args.num_queues,
+                                        args.ipv6, weights) if args.symmetric else
+                 evaluate([args.key], tuples, args.htable_size, args.num_queues,
+                          ipv6=args.ipv6, weights=weights))
+        base = balance(given, args.htable_size, args.num_queues)
         print("given key: max_load %.4f chi2 %.2f queues used %d"
               % (base["max_load"][0], base["chi2"][0], base["used"][0]))
     for r in ranked:

@@ -20,7 +20,14 @@ clipped to u32) and with all-ones weights, against the unweighted entries at the
 the same process (alternating windows, medians), and against the host loop they replace: one
 rss_hash_device launch per key, its queue column copied back and np.bincount(weights=) on the
 host, timed over 16 keys and scaled to K.  One shape per invocation, so that a job gives each
-shape a time limit of its own."""
+shape a time limit of its own.
+       python tools/keysearch_bench.py --symmetric [n] [H] [Q] [big_n]
+--symmetric times the exhaustive symmetric-key ranking on n resident uniform flows: the fold
+alone (rss_symmetric_fold_device: IPv4, IPv6, IPv4 with weights), the scan of all 65536 patterns
+alone (rss_symmetric_search_device) and the two together, against the only way there was before:
+one rss_key_search_device launch over the 65536 periodic keys' windows (built once, outside the
+timing; its counts compared equal to the new loads first).  Alternating windows between device
+events, medians.  Then the fold at big_n flows against the tuple bytes it has to read."""
 import json
 import os
 import sys
@@ -184,6 +191,84 @@ def weighted_main(argv):
         "search_weighted_key_flow_evals_per_s": K * n / (med["search_zipf"] / 1e3),
         "neighbourhood_weighted_key_flow_evals_per_s": 128 * n / (med["neighbourhood_zipf"] / 1e3)}))
 
+
+def symmetric_main(argv):
+    """--symmetric [n] [H] [Q] [big_n]: see the module docstring."""
+    n, H, Q, big_n = ([int(a) for a in argv] + [1 << 20, 128, 24, 1 << 26][len(argv):])[:4]
+    P = _native.SYMMETRIC_PATTERNS
+    dev = torch.device("cuda:0")
+    s = torch.cuda.current_stream(dev).cuda_stream
+    t4 = torch.empty(3 * n, dtype=torch.int32, device=dev)
+    _native.generate_device(1, 0, n, t4.data_ptr(), s)
+    t6 = torch.randint(0, 2**32, (9 * n,), dtype=torch.int64, device=dev,
+                       generator=torch.Generator(dev).manual_seed(1)).to(torch.int32)
+    host_w = np.minimum(np.random.default_rng(3).zipf(1.3, n), 0xFFFFFFFF).astype(np.uint32)
+    d_w = torch.from_numpy(host_w.view(np.int32)).to(dev)
+    width = _native.queue_modulus(H, Q)[1]
+    folds = {k: torch.empty(P, dtype=torch.int64, device=dev) for k in ("v4", "v6", "v4w")}
+    loads = torch.empty((P, width), dtype=torch.int64, device=dev)
+    # the periodic keys' windows in closed form: window i = rotl16(p, i % 16) twice over
+    p = np.arange(P, dtype=np.uint32)[:, None]
+    r = (np.arange(96, dtype=np.uint32) % 16)[None, :]
+    g = ((p << r) | (p >> (16 - r))) & 0xFFFF
+    win = (g << 16) | g
+    for pat in (0, 1, 0x6d5a, 0xFFFF):
+        key = _native.prepare_key(keysearch.symmetric_key(pat))
+        assert np.array_equal(win[pat], np.ctypeslib.as_array(key.window))
+    windows = torch.from_numpy(win.view(np.int32)).to(dev)
+    counts = torch.empty((P, width), dtype=torch.int64, device=dev)
+
+    def fold(kind):
+        tuples, words, w = {"v4": (t4, 3, None), "v6": (t6, 9, None), "v4w": (t4, 3, d_w)}[kind]
+        return lambda: _native.symmetric_fold_device(
+            tuples.data_ptr(), words, _native.FIELDS_ALL, w.data_ptr() if w is not None else None,
+            n, folds[kind].data_ptr(), 0, s)
+
+    scan = lambda: _native.symmetric_search_device(folds["v4"].data_ptr(), 0, P, H, Q,  # noqa: E731
+                                                   loads.data_ptr(), s)
+    contenders = {
+        "fold_ipv4": (fold("v4"), 200), "fold_ipv6": (fold("v6"), 200),
+        "fold_ipv4_weighted": (fold("v4w"), 200), "scan": (scan, 20),
+        "fold_and_scan": (lambda: (fold("v4")(), scan()), 20),
+        "search_65536_keys": (lambda: _native.key_search_device(
+            windows.data_ptr(), P, t4.data_ptr(), n, H, Q, counts.data_ptr(), s), 2)}
+    for fn, _ in contenders.values():  # warm every shape, then check before timing
+        fn()
+        fn()
+    torch.cuda.synchronize()
+    assert torch.equal(loads, counts) and bool((loads.sum(dim=1) == n).all())
+    assert int(folds["v6"].sum()) == n and int(folds["v4w"].sum()) == int(host_w.sum(dtype=np.uint64))
+    rounds = 5
+    times = {name: [] for name in contenders}
+    for _ in range(rounds):
+        for name, (fn, reps) in contenders.items():
+            times[name].append(window_ms(fn, reps))
+    med = {name: float(np.median(v)) for name, v in times.items()}
+    # the fold at big_n flows: the tuples are the bytes it has to read (each quarter reads them)
+    del t6, windows, counts
+    big = torch.empty(3 * big_n, dtype=torch.int32, device=dev)
+    _native.generate_device(2, 0, big_n, big.data_ptr(), s)
+    big_fold = lambda: _native.symmetric_fold_device(big.data_ptr(), 3, _native.FIELDS_ALL, None,  # noqa
+                                                     big_n, folds["v4"].data_ptr(), 0, s)
+    big_fold()
+    torch.cuda.synchronize()
+    assert int(folds["v4"].sum()) == big_n
+    big_ms = [window_ms(big_fold, 10) for _ in range(rounds)]
+    print(json.dumps({
+        "mode": "symmetric", "flows": n, "htable": H, "queues": Q, "patterns": P,
+        "reps_per_window": {name: reps for name, (_, reps) in contenders.items()},
+        "window_ms": times, "median_ms": med,
+        "scan_fold_pattern_evals_per_s": P * P / (med["scan"] / 1e3),
+        "search_key_flow_evals_per_s": P * n / (med["search_65536_keys"] / 1e3),
+        "speedup_vs_search_65536_keys": med["search_65536_keys"] / med["fold_and_scan"],
+        "big_fold": {"flows": big_n, "window_ms": big_ms, "median_ms": float(np.median(big_ms)),
+                     "tuple_bytes": 12 * big_n,
+                     "tuple_gb_per_s": 12 * big_n / (float(np.median(big_ms)) / 1e3) / 1e9}}))
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "--symmetric":
+    symmetric_main(sys.argv[2:])
+    sys.exit(0)
 
 if len(sys.argv) > 1 and sys.argv[1] == "--weighted":
     weighted_main(sys.argv[2:])
