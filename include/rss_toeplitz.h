@@ -311,6 +311,33 @@ int rss_symmetric_search_device(const uint64_t* d_folds, uint32_t first_pattern,
                                 uint64_t* d_loads, void* stream);
 
 /*
+ * Flow aggregation: packets to the flows the weighted entries above take.  Groups n tuples
+ * (d_tuples: `words` host-order words each, 3: rss_tuple4, 9: rss_tuple6) by value and sums a
+ * weight per group: d_weights n uint32, or NULL for 1 per packet (the loads are then packet
+ * counts).  Output, every buffer sized for n: *d_nflows (device memory) = F, the number of
+ * distinct tuples; d_flows[F] the distinct tuples in first-seen order; d_loads[F] the exact
+ * 64-bit sum of each flow's weights; d_first[F] the index of each flow's first packet (strictly
+ * increasing).  A pure function of the input: bit-exact, whatever the scheduling.
+ * A hash set of packet indices (linear probing; claim by compare-and-swap, all words compared,
+ * atomic minimum: no lane ever waits for another) behind a per-workgroup LDS combiner, then a
+ * count / scan / emit compaction; DESIGN.md §7. d_workspace: workspace_bytes >=
+ * rss_flow_aggregate_workspace_bytes(n, words) bytes of 8-byte aligned device memory, any
+ * contents (the call clears what it uses by a kernel, so it can be captured into a graph), used
+ * by one call at a time.  Tuples and weights both 16-byte aligned take dwordx4 loads.  n == 0
+ * only writes *d_nflows = 0 (tuples, flows, loads and first may be NULL).
+ * rss_flow_aggregate_host: the same on host buffers under the context's lock (h_flows, h_loads,
+ * h_first sized for n; only *nflows rows are written).  Synchronous.
+ * RSS_EINVAL, before any device work, with rss_last_error naming the entry and the cause: words
+ * not 3 or 9; n > 2^30; a NULL pointer other than weights (and, with n == 0, other than the
+ * workspace and nflows); a workspace that is misaligned or too small; a NULL ctx.
+ */
+int rss_flow_aggregate_workspace_bytes(size_t n, uint32_t words, size_t* out);
+int rss_flow_aggregate_device(const void* d_tuples, uint32_t words, const uint32_t* d_weights,
+                              size_t n, void* d_flows, uint64_t* d_loads, uint32_t* d_first,
+                              uint64_t* d_nflows, void* d_workspace, size_t workspace_bytes,
+                              void* stream);
+
+/*
  * IPv6.  36-byte input = src addr (16 B) | dst addr (16 B) |
  * src port | dst port, the layout of the Microsoft RSS IPv6 hash; stored as nine
  * host-order words whose big-endian bytes are that input (w[0..3] src, w[4..7]
@@ -577,6 +604,12 @@ int rss_symmetric_search_host(rss_ctx* ctx, const void* h_tuples, uint32_t words
                               const uint32_t* h_weights, size_t n, uint32_t first_pattern,
                               uint32_t npatterns, uint32_t htable, uint32_t nqueues,
                               uint64_t* h_loads);
+
+/* rss_flow_aggregate_device on host buffers (described with it): uploads the tuples and the
+ * weights, aggregates, downloads the *nflows rows.  Synchronous. */
+int rss_flow_aggregate_host(rss_ctx* ctx, const void* h_tuples, uint32_t words,
+                            const uint32_t* h_weights, size_t n, void* h_flows, uint64_t* h_loads,
+                            uint32_t* h_first, size_t* nflows);
 
 /* rss_key_search6_device on host buffers (keys: nkeys prepared rss_key6; h_counts: nkeys x
  * nqueues uint64), as rss_key_search_host.  Synchronous.  Refuses what the device entry

@@ -45,7 +45,8 @@ EXPORTED_SYMBOLS = (
     "rss_key_search_weighted_device", "rss_key_neighbourhood_weighted_device",
     "rss_key_search_weighted_host", "rss_key_neighbourhood_weighted_host",
     "rss_symmetric_key", "rss_symmetric_fold_device", "rss_symmetric_search_device",
-    "rss_symmetric_search_host",
+    "rss_symmetric_search_host", "rss_flow_aggregate_workspace_bytes",
+    "rss_flow_aggregate_device", "rss_flow_aggregate_host",
 )
 SYMMETRIC_PATTERNS = 65536  # RSS_SYMMETRIC_PATTERNS: 16-bit key patterns = fold values
 KEY_NEIGHBOURS = 128  # RSS_KEY_NEIGHBOURS: the key bits an IPv4 hash reads
@@ -125,6 +126,10 @@ def _bind(lib):
         "rss_symmetric_search_device": ([vp, u32, u32, u32, u32, vp, vp], ctypes.c_int),
         "rss_symmetric_search_host": ([vp, vp, u32, u32, vp, sz, u32, u32, u32, u32, vp],
                                       ctypes.c_int),
+        "rss_flow_aggregate_workspace_bytes": ([sz, u32, ctypes.POINTER(sz)], ctypes.c_int),
+        "rss_flow_aggregate_device": ([vp, u32, vp, sz, vp, vp, vp, vp, vp, sz, vp], ctypes.c_int),
+        "rss_flow_aggregate_host": ([vp, vp, u32, vp, sz, vp, vp, vp, ctypes.POINTER(sz)],
+                                    ctypes.c_int),
         "rss_key_search6_device": ([vp, sz, vp, sz, u32, u32, vp, vp], ctypes.c_int),
         "rss_key_search6_host": ([vp, vp, sz, vp, sz, u32, u32, vp], ctypes.c_int),
         "rss_key_neighbourhood6_device": ([ctypes.POINTER(RssKey6), vp, sz, u32, u32, vp, vp],
@@ -612,6 +617,26 @@ class HostContext:
             npatterns, htable, nqueues, out.ctypes.data), "rss_symmetric_search_host")
         return out
 
+    def aggregate_flows(self, tuples, weights=None, ipv6=False):
+        """Packets to flows (``rss_flow_aggregate_host``): the distinct ``tuples`` in first-seen
+        order (uint32[F, 3], ``ipv6``: [F, 9]), each flow's summed u32 ``weights`` (uint64[F];
+        packet counts without weights) and its first packet's index (uint32[F])."""
+        words = 9 if ipv6 else 3
+        arr = _tuples6(tuples) if ipv6 else np.ascontiguousarray(tuples)
+        if not ipv6 and arr.dtype != TUPLE_DTYPE:
+            arr = np.ascontiguousarray(arr, dtype=np.uint32).reshape(-1, 3)
+        n = len(arr)
+        w = tuple_weights(weights, n) if weights is not None else None
+        flows = np.empty((n, words), dtype=np.uint32)
+        loads = np.empty(n, dtype=np.uint64)
+        first = np.empty(n, dtype=np.uint32)
+        found = ctypes.c_size_t()
+        _check(self._lib.rss_flow_aggregate_host(
+            self._ctx, arr.ctypes.data, words, ptr(w), n, flows.ctypes.data, loads.ctypes.data,
+            first.ctypes.data, ctypes.byref(found)), "rss_flow_aggregate_host")
+        f = found.value
+        return flows[:f].copy(), loads[:f].copy(), first[:f].copy()
+
 
 def symmetric_key(pattern, length=40):
     """The ``length`` bytes of the symmetric key of 16-bit ``pattern`` (``rss_symmetric_key``):
@@ -855,6 +880,24 @@ def symmetric_search_device(folds_ptr, first_pattern, npatterns, htable, nqueues
     htable, nqueues = queue_modulus(htable, nqueues)
     _check(load().rss_symmetric_search_device(folds_ptr, first_pattern, npatterns, htable, nqueues,
                                               loads_ptr, stream), "rss_symmetric_search_device")
+
+
+def flow_aggregate_workspace_bytes(n, words=3):
+    """Bytes of the workspace ``rss_flow_aggregate_device`` needs for ``n`` packets."""
+    out = ctypes.c_size_t()
+    _check(load().rss_flow_aggregate_workspace_bytes(n, words, ctypes.byref(out)),
+           "rss_flow_aggregate_workspace_bytes")
+    return out.value
+
+
+def flow_aggregate_device(tuples_ptr, words, weights_ptr, n, flows_ptr, loads_ptr, first_ptr,
+                          nflows_ptr, workspace_ptr, workspace_bytes, stream=None):
+    """Stream-ordered ``rss_flow_aggregate_device`` on raw device pointers (ints): ``words`` 3
+    or 9 per tuple, ``weights_ptr`` n uint32 or None; ``flows_ptr`` / ``loads_ptr`` (uint64) /
+    ``first_ptr`` (uint32) sized for n, ``nflows_ptr`` one uint64."""
+    _check(load().rss_flow_aggregate_device(tuples_ptr, words, weights_ptr, n, flows_ptr,
+                                            loads_ptr, first_ptr, nflows_ptr, workspace_ptr,
+                                            workspace_bytes, stream), "rss_flow_aggregate_device")
 
 
 def key_search6_device(windows_ptr, nkeys, tuples_ptr, n, htable, nqueues, counts_ptr,

@@ -1,5 +1,6 @@
 // rss_engine.h -- the engine's launchers (rss_toeplitz.hip, rss_keysearch.hip,
-// rss_keysearch6.hip, rss_neighbourhood.hip, rss_keysearch_weighted.hip, rss_symmetric.hip) as the C ABI (rss_host.hip) calls
+// rss_keysearch6.hip, rss_neighbourhood.hip, rss_keysearch_weighted.hip, rss_symmetric.hip,
+// rss_flow_aggregate.hip) as the C ABI (rss_host.hip) calls
 // them, and the HIP error macro both use.  Internal, not ABI.
 #pragma once
 
@@ -66,6 +67,13 @@ RSS_HIDDEN int launch_symmetric_fold(const void* d_tuples, uint32_t words, uint3
 RSS_HIDDEN int launch_symmetric_search(const uint64_t* d_folds, uint32_t first_pattern,
                                        uint32_t npatterns, uint32_t htable, uint32_t nqueues,
                                        uint64_t* d_loads, hipStream_t stream);
+// rss_flow_aggregate_workspace_bytes / rss_flow_aggregate_device (rss_flow_aggregate.hip;
+// arguments validated by the caller, the workspace 8-byte aligned and large enough)
+RSS_HIDDEN size_t flow_aggregate_workspace_bytes(size_t n);
+RSS_HIDDEN int launch_flow_aggregate(const void* d_tuples, uint32_t words,
+                                     const uint32_t* d_weights, size_t n, void* d_flows,
+                                     uint64_t* d_loads, uint32_t* d_first, uint64_t* d_nflows,
+                                     void* d_workspace, hipStream_t stream);
 // d_counts[0, cells) = 0 by a kernel (rss_neighbourhood.hip): capturable, unlike a memset node
 RSS_HIDDEN int launch_zero_counts(uint64_t* d_counts, uint64_t cells, hipStream_t stream);
 // rss_generate_tuples (n > 0, d_tuples non-NULL)

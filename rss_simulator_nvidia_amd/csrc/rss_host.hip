@@ -156,6 +156,18 @@ int check_symmetric_search(const char* who, uint32_t first_pattern, uint32_t npa
     return RSS_OK;
 }
 
+// rss_flow_aggregate_workspace_bytes / _device / _host: the packets
+constexpr size_t kAggregateMaxPackets = (size_t)1 << 30;  // indices and 2n slots fit u32
+int check_flow_aggregate(const char* who, const void* tuples, uint32_t words, size_t n) {
+    if (words != 3 && words != 9)
+        return rss_set_error(RSS_EINVAL, "%s: words must be 3 (IPv4) or 9 (IPv6), got %u", who,
+                             words);
+    if (n > kAggregateMaxPackets)
+        return rss_set_error(RSS_EINVAL, "%s: %zu packets exceed the limit of 2^30", who, n);
+    if (n && !tuples) return rss_set_error(RSS_EINVAL, "%s: tuples is NULL", who);
+    return RSS_OK;
+}
+
 // The key-search host entries (IPv4 / IPv6, search / neighbourhood, weighted or not): under the
 // context's lock upload `windows` (search only; empty otherwise), the tuples and their weights
 // (weighted only; NULL otherwise), `launch(d_windows, d_tuples, d_weights, d_counts, stream)`,
@@ -437,6 +449,35 @@ int rss_symmetric_search_device(const uint64_t* d_folds, uint32_t first_pattern,
     if (rc) return rc;
     return rss::launch_symmetric_search(d_folds, first_pattern, npatterns, htable, nqueues, d_loads,
                                         static_cast<hipStream_t>(stream));
+}
+
+int rss_flow_aggregate_workspace_bytes(size_t n, uint32_t words, size_t* out) {
+    const char* who = "rss_flow_aggregate_workspace_bytes";
+    if (!out) return rss_set_error(RSS_EINVAL, "%s: NULL argument", who);
+    int rc = check_flow_aggregate(who, out, words, n);  // (no tuples here: any non-NULL pointer)
+    if (rc) return rc;
+    *out =rss::flow_aggregate_workspace_bytes(n);
+    return RSS_OK;
+}
+
+int rss_flow_aggregate_device(const void* d_tuples, uint32_t words, const uint32_t* d_weights,
+                              size_t n, void* d_flows, uint64_t* d_loads, uint32_t* d_first,
+                              uint64_t* d_nflows, void* d_workspace, size_t workspace_bytes,
+                              void* stream) {
+    const char* who = "rss_flow_aggregate_device";
+    int rc = check_flow_aggregate(who, d_tuples, words, n);
+    if (rc) return rc;
+    if (!d_nflows) return rss_set_error(RSS_EINVAL, "%s: nflows is NULL", who);
+    if (n && (!d_flows || !d_loads || !d_first))
+        return rss_set_error(RSS_EINVAL, "%s: flows, loads or first is NULL", who);
+    if (!d_workspace || ((uintptr_t)d_workspace & 7u))
+        return rss_set_error(RSS_EINVAL, "%s: workspace NULL or not 8-byte aligned", who);
+    const size_t need = rss::flow_aggregate_workspace_bytes(n);
+    if (workspace_bytes < need)
+        return rss_set_error(RSS_EINVAL, "%s: workspace of %zu bytes, %zu packets need %zu", who,
+                             workspace_bytes, n, need);
+    return rss::launch_flow_aggregate(d_tuples, words, d_weights, n, d_flows, d_loads, d_first,
+                                      d_nflows, d_workspace, static_cast<hipStream_t>(stream));
 }
 
 int rss_generate_tuples(uint64_t seed, uint64_t first_index, size_t n, rss_tuple4* d_tuples,
@@ -961,6 +1002,63 @@ int rss_symmetric_search_host(rss_ctx* ctx, const void* h_tuples, uint32_t words
                             h_loads, launch, h_weights, fold_bytes);
     return key_host_run(who, ctx, {}, static_cast<const rss_tuple6*>(h_tuples), n, load_bytes,
                         h_loads, launch, h_weights, fold_bytes);
+}
+
+int rss_flow_aggregate_host(rss_ctx* ctx, const void* h_tuples, uint32_t words,
+                            const uint32_t* h_weights, size_t n, void* h_flows, uint64_t* h_loads,
+                            uint32_t* h_first, size_t* nflows) {
+    const char* who = "rss_flow_aggregate_host";
+    if (!ctx) return rss_set_error(RSS_EINVAL, "%s: context is NULL", who);
+    if (!nflows) return rss_set_error(RSS_EINVAL, "%s: nflows is NULL", who);
+    int rc = check_flow_aggregate(who, h_tuples, words, n);
+    if (rc) return rc;
+    if (n && (!h_flows || !h_loads || !h_first))
+        return rss_set_error(RSS_EINVAL, "%s: flows, loads or first is NULL", who);
+    *nflows = 0;
+    if (n == 0) return RSS_OK;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    RSS_HIP_CHECK(hipSetDevice(ctx->device));
+    // one allocation: tuples | weights | flows | loads | first | nflows | workspace, each part
+    // 16-byte aligned
+    auto pad = [](size_t bytes) { return (bytes + 15) & ~(size_t)15; };
+    const size_t row = (size_t)words * sizeof(uint32_t);
+    const size_t parts[7] = {pad(n * row), pad(h_weights ? n * 4 : 0), pad(n * row), pad(n * 8),
+                             pad(n * 4), 16, rss::flow_aggregate_workspace_bytes(n)};
+    size_t off[8] = {0};
+    for (int i = 0; i < 7; ++i) off[i + 1] = off[i] + parts[i];
+    char* d = nullptr;
+    hipStream_t s = ctx->stream[0];
+    hipError_t e = hipMalloc(&d, off[7]);
+    if (e == hipSuccess) e = hipMemcpyAsync(d, h_tuples, n * row, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && h_weights)
+        e = hipMemcpyAsync(d + off[1], h_weights, n * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) {
+        rc = rss::launch_flow_aggregate(d, words, h_weights ? (const uint32_t*)(d + off[1]) : nullptr,
+                                        n, d + off[2], (uint64_t*)(d + off[3]),
+                                        (uint32_t*)(d + off[4]), (uint64_t*)(d + off[5]),
+                                        d + off[6], s);
+        uint64_t found = 0;
+        if (rc == RSS_OK) {
+            e = hipMemcpyAsync(&found, d + off[5], sizeof found, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+        }
+        if (rc == RSS_OK && e == hipSuccess) {  // the F rows only
+            e = hipMemcpyAsync(h_flows, d + off[2], found * row, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(h_loads, d + off[3], found * 8, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(h_first, d + off[4], found * 4, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e == hipSuccess) *nflows = (size_t)found;
+        }
+    }
+    if (e != hipSuccess && rc == RSS_OK)
+        rc = rss_set_error(e == hipErrorOutOfMemory ? RSS_ENOMEM : RSS_EIO, "%s: %s", who,
+                           hipGetErrorString(e));
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(d);
+    if (rc) *nflows = 0;
+    return rc;
 }
 
 int rss_key_search6_host(rss_ctx* ctx, const rss_key6* keys, size_t nkeys,

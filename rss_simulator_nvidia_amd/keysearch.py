@@ -24,6 +24,11 @@ capture: its unique flows, weighted by their packets) rank and refine by the **l
 key puts on a queue instead of the number of flows (``rss_key_search_weighted_device``,
 ``rss_key_neighbourhood_weighted_device``; IPv4 flows).
 
+``--aggregate`` takes a CSV with one row per **packet**: the rows are folded to flows on the
+GPU (``rss_flow_aggregate_device``: a hash set of packet indices, first-seen order) and each
+flow's load is the sum of its rows' ``--weight-column``, or its row count without one.
+``--pcap`` de-duplicates its packets the same way.
+
 ``--symmetric`` ranks the 65536 symmetric keys instead -- a 16-bit pattern repeated over the
 key (DPDK's ``6d:5a:6d:5a:...``), which sends both directions of a connection to one queue.
 Their hash depends only on the XOR of a tuple's 16-bit half-words, so the flows are folded
@@ -339,7 +344,14 @@ def main(argv=None):
                    help="rank all 65536 symmetric keys (a 16-bit pattern repeated, like DPDK's "
                         "6d:5a:...) instead of random candidates: both directions of a "
                         "connection share a queue; exhaustive, IPv4 or IPv6, weighted or not")
+    p.add_argument("--aggregate", action="store_true",
+                   help="the CSV holds one row per packet: fold the rows to flows (on the GPU) "
+                        "and rank by load, the sum of --weight-column per flow or the rows per "
+                        "flow without it")
     args = p.parse_args(argv)
+    if args.aggregate and args.pcap:
+        p.error("--aggregate folds the rows of a CSV: not allowed with --pcap, whose packets "
+                "are always folded to flows")
     if args.symmetric and args.refine > 0:
         p.error("--refine cannot be combined with --symmetric: a single-bit flip breaks the "
                 "key's symmetry")
@@ -349,14 +361,15 @@ def main(argv=None):
         import torch
         torch.cuda.init()
     weights = None
-    if args.ipv6 and (args.pcap or args.weight_column) and not args.symmetric:
+    if args.ipv6 and (args.pcap or args.weight_column or args.aggregate) and not args.symmetric:
         p.error("--ipv6 cannot be combined with --pcap or --weight-column: weighted key "
                 "search serves IPv4 flows only")
     if args.pcap and args.weight_column:
         p.error("--weight-column names a CSV column: not allowed with --pcap")
     if args.pcap:
         from rss_simulator_nvidia_amd.pcap import read_flows
-        tuples, _, _, weights = read_flows(args.pcap, ipv6=args.ipv6, packet_counts=True)
+        tuples, _, _, weights = read_flows(args.pcap, ipv6=args.ipv6, packet_counts=True,
+                                           on_device=True)
     elif args.weight_column:
         try:
             tuples, weights = (load_weighted_csv6 if args.ipv6 else load_weighted_csv)(
@@ -365,6 +378,13 @@ def main(argv=None):
             p.error("--weight-column %s: %s" % (args.weight_column, err))
     else:
         tuples = load_tuples(args.ips_file, args.ipv6)
+    if args.aggregate:
+        from rss_simulator_nvidia_amd.flows import aggregate
+        tuples, loads, _ = aggregate(tuples, weights, args.ipv6)
+        try:
+            weights = _native.tuple_weights(loads, len(loads))  # the weighted search takes u32
+        except ValueError as err:
+            p.error("--aggregate: a flow's summed weight: %s" % err)
     extra = [args.key] if args.key else []
     if args.symmetric:
         ranked = symmetric_search(tuples, args.htable_size, args.num_queues, ipv6=args.ipv6,

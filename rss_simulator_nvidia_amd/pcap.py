@@ -30,12 +30,13 @@ def parse_l4(spec):
         raise ValueError("L4 protocols must be a comma list of tcp, udp, sctp (or none)")
 
 
-def read_flows(path, l4=None, unique=True, ipv6=False, packet_counts=False):
+def read_flows(path, l4=None, unique=True, ipv6=False, packet_counts=False, on_device=False):
     """Packed tuples of a capture's IPv4 packets (``TUPLE_DTYPE``), or with ``ipv6`` of its
     IPv6 packets (``TUPLE6_DTYPE``) -> (tuples, protocols, skipped packets).  With
     ``packet_counts`` a fourth item: uint32 packets per returned tuple (the weights of
     ``keysearch``'s load ranking) -- each unique flow's packets in the same first-seen order,
-    or ones without ``unique``."""
+    or ones without ``unique``.  ``on_device``: the de-duplication runs on the GPU
+    (``flows.aggregate``) instead of ``np.unique`` -- the same result."""
     try:
         data = np.fromfile(path, dtype=np.uint8)
     except OSError as err:
@@ -49,7 +50,11 @@ def read_flows(path, l4=None, unique=True, ipv6=False, packet_counts=False):
         tuples = tuples.copy()
         tuples["ports"][~np.isin(protos, list(keep))] = 0
     packets = np.ones(len(tuples), dtype=np.uint32)
-    if unique and len(tuples):
+    if unique and len(tuples) and on_device:
+        from rss_simulator_nvidia_amd import flows
+        tuples, per_flow, first = flows.aggregate(tuples, ipv6=ipv6)
+        protos, packets = protos[first], per_flow.astype(np.uint32)
+    elif unique and len(tuples):
         raw = np.ascontiguousarray(tuples).view(np.dtype((np.void, tuples.dtype.itemsize)))
         _, first, per_flow = np.unique(raw, return_index=True, return_counts=True)
         by_first = np.argsort(first, kind="stable")  # np.unique sorts by value: back to first seen
