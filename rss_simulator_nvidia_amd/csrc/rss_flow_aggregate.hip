@@ -44,6 +44,7 @@
 #include <algorithm>
 
 #include "rss_engine.h"
+#include "rss_flow_hash.h"
 #include "rss_kernel_common.h"
 #include "rss_keysearch_tables.h"
 
@@ -71,26 +72,7 @@ struct AggWorkspace {  // views into the caller's workspace
     uint32_t ntiles;
 };
 
-__device__ __forceinline__ uint32_t agg_mix(uint32_t h, uint32_t w) {
-    h = (h ^ w) * 0x9E3779B1u;
-    return (h << 15) | (h >> 17);
-}
-
-__device__ __forceinline__ uint32_t agg_finish(uint32_t h) {  // murmur3's finaliser
-    h ^= h >> 16;
-    h *= 0x85EBCA6Bu;
-    h ^= h >> 13;
-    h *= 0xC2B2AE35u;
-    return h ^ (h >> 16);
-}
-
-template <int kWords>
-__device__ __forceinline__ uint32_t agg_hash(const uint32_t* t) {
-    uint32_t h = 0x2545F491u;
-#pragma unroll
-    for (int k = 0; k < kWords; ++k) h = agg_mix(h, t[k]);
-    return agg_finish(h);
-}
+// agg_hash<kWords> (agg_mix, agg_finish): rss_flow_hash.h
 
 template <int kWords>
 __device__ __forceinline__ bool agg_equal(const uint32_t* a, const uint32_t* b) {
