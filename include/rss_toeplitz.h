@@ -414,6 +414,48 @@ int rss_key_neighbourhood6_device(const rss_key6* key, const rss_tuple6* d_tuple
                                   void* stream);
 
 /*
+ * A key's byte neighbourhood (key search's wider local step; keysearch.refine(step="byte")
+ * descends on it): the per-queue counts of the same n device-resident tuples under every key
+ * that differs from `key` in one byte -- all 256 values of each of bytes [first_byte,
+ * first_byte + nbytes) of the RSS_KEY_BYTES (IPv6: RSS_KEY6_BYTES) bytes a hash reads, the way
+ * NICs are programmed (ethtool -X hkey aa:bb:...).  A byte's 256 values cover every change of
+ * up to 8 bits inside it, its 8 single-bit flips among them.  Toeplitz is linear in the key:
+ * with d = v ^ key[B], hash(key[B := v], x) = hash(key, x) ^ XOR over the set bits 0x80 >> k of
+ * d of delta_{8B+k}(x), the single-bit entries' deltas; one launch hashes every tuple once per
+ * chunk of up to 32 values and walks the chunk in Gray-code order, one XOR per value.
+ * d_counts: nbytes * 256 x nqueues uint64, overwritten (cleared by a kernel of the same call,
+ * then counted: the call can be captured into a graph): row 256 * (B - first_byte) + v holds
+ * the counts under the key whose byte B is v and whose other bytes are unchanged, so row
+ * 256 * (B - first_byte) + key[B] is the key itself for every B.  Key bit 127 (IPv6: 319) feeds
+ * no hash: rows v and v ^ 1 of byte 15 (IPv6: 39) are equal.  queue = hash % htable % nqueues
+ * and columns [min(htable, nqueues), nqueues) are zero.  The weighted entry writes d_loads, the
+ * exact 64-bit sums of the u32 weights (d_weights: n uint32, any values), instead.
+ * Exact for any htable, nqueues >= 1, any n (0 only clears) and any 4-byte aligned pointers;
+ * tuples (and weights) 16-byte aligned take the 4-tuples-per-lane path.  Bins as the single-bit
+ * entries: lane-private LDS bins for 32 values per workgroup up to 39 queues (IPv6 38, weighted
+ * 19), 16 up to 78 (76, 39), ... 1 up to 1259 (1217, 629), shared LDS bins up to 40288 (38944,
+ * 20144), global 64-bit atomics past them.
+ * RSS_EINVAL, before any device work, with rss_last_error naming the entry and the cause:
+ * whatever the matching single-bit entry refuses (key, counts or loads NULL; n > 0 with tuples
+ * or weights NULL; htable or nqueues 0; key->len < 16 (IPv6: < 40); a field-selected or
+ * non-plain key), and nbytes == 0 or first_byte + nbytes > 16 (IPv6: > 40).  IPv6 tuples with
+ * weights are out of scope.
+ */
+#define RSS_KEY_BYTES 16    /* key bytes an IPv4 hash reads  */
+#define RSS_KEY6_BYTES 40   /* ... an IPv6 hash reads        */
+int rss_key_byte_neighbourhood_device(const rss_key* key, uint32_t first_byte, uint32_t nbytes,
+                                      const rss_tuple4* d_tuples, size_t n, uint32_t htable,
+                                      uint32_t nqueues, uint64_t* d_counts, void* stream);
+int rss_key_byte_neighbourhood6_device(const rss_key6* key, uint32_t first_byte, uint32_t nbytes,
+                                       const rss_tuple6* d_tuples, size_t n, uint32_t htable,
+                                       uint32_t nqueues, uint64_t* d_counts, void* stream);
+int rss_key_byte_neighbourhood_weighted_device(const rss_key* key, uint32_t first_byte,
+                                               uint32_t nbytes, const rss_tuple4* d_tuples,
+                                               const uint32_t* d_weights, size_t n,
+                                               uint32_t htable, uint32_t nqueues,
+                                               uint64_t* d_loads, void* stream);
+
+/*
  * Host-memory convenience path (CSV in -> CSV out): owns device buffers.
  * Thread safety: any number of host threads may call the entry points that take one
  * context at once; each call holds the context's lock from entry to return, so calls on
@@ -623,6 +665,22 @@ int rss_key_search6_host(rss_ctx* ctx, const rss_key6* keys, size_t nkeys,
  * first; n == 0 zeroes h_counts on the host. */
 int rss_key_neighbourhood6_host(rss_ctx* ctx, const rss_key6* key, const rss_tuple6* h_tuples,
                                 size_t n, uint32_t htable, uint32_t nqueues, uint64_t* h_counts);
+
+/* The rss_key_byte_neighbourhood*_device entries on host buffers (h_counts / h_loads: nbytes *
+ * 256 x nqueues uint64; h_weights: n uint32), as rss_key_neighbourhood_host: take the context's
+ * lock, upload the tuples (and weights), launch, copy the rows back.  Synchronous.  The same
+ * validation (and a NULL ctx) is refused first; n == 0 zeroes the output on the host. */
+int rss_key_byte_neighbourhood_host(rss_ctx* ctx, const rss_key* key, uint32_t first_byte,
+                                    uint32_t nbytes, const rss_tuple4* h_tuples, size_t n,
+                                    uint32_t htable, uint32_t nqueues, uint64_t* h_counts);
+int rss_key_byte_neighbourhood6_host(rss_ctx* ctx, const rss_key6* key, uint32_t first_byte,
+                                     uint32_t nbytes, const rss_tuple6* h_tuples, size_t n,
+                                     uint32_t htable, uint32_t nqueues, uint64_t* h_counts);
+int rss_key_byte_neighbourhood_weighted_host(rss_ctx* ctx, const rss_key* key,
+                                             uint32_t first_byte, uint32_t nbytes,
+                                             const rss_tuple4* h_tuples,
+                                             const uint32_t* h_weights, size_t n, uint32_t htable,
+                                             uint32_t nqueues, uint64_t* h_loads);
 
 /* rss_hash6_device on host buffers: rss_hash_host's contract and path (the same staging,
  * small-batch path, pipeline and direct DMA of page-locked buffers), 36-byte tuples. */

@@ -47,10 +47,15 @@ EXPORTED_SYMBOLS = (
     "rss_symmetric_key", "rss_symmetric_fold_device", "rss_symmetric_search_device",
     "rss_symmetric_search_host", "rss_flow_aggregate_workspace_bytes",
     "rss_flow_aggregate_device", "rss_flow_aggregate_host",
+    "rss_key_byte_neighbourhood_device", "rss_key_byte_neighbourhood6_device",
+    "rss_key_byte_neighbourhood_weighted_device", "rss_key_byte_neighbourhood_host",
+    "rss_key_byte_neighbourhood6_host", "rss_key_byte_neighbourhood_weighted_host",
 )
 SYMMETRIC_PATTERNS = 65536  # RSS_SYMMETRIC_PATTERNS: 16-bit key patterns = fold values
 KEY_NEIGHBOURS = 128  # RSS_KEY_NEIGHBOURS: the key bits an IPv4 hash reads
 KEY6_NEIGHBOURS = 320  # RSS_KEY6_NEIGHBOURS: the key bits an IPv6 hash reads
+KEY_BYTES = 16  # RSS_KEY_BYTES: the key bytes an IPv4 hash reads
+KEY6_BYTES = 40  # RSS_KEY6_BYTES: the key bytes an IPv6 hash reads
 FIELD_SRC_IP, FIELD_DST_IP, FIELD_SRC_PORT, FIELD_DST_PORT = 1, 2, 4, 8
 FIELDS_IP, FIELDS_ALL = 3, 15
 ENOTSUP = -95
@@ -121,6 +126,18 @@ def _bind(lib):
         "rss_key_search_weighted_host": ([vp, vp, sz, vp, vp, sz, u32, u32, vp], ctypes.c_int),
         "rss_key_neighbourhood_weighted_host": ([vp, key_p, vp, vp, sz, u32, u32, vp],
                                                 ctypes.c_int),
+        "rss_key_byte_neighbourhood_device": ([key_p, u32, u32, vp, sz, u32, u32, vp, vp],
+                                              ctypes.c_int),
+        "rss_key_byte_neighbourhood_host": ([vp, key_p, u32, u32, vp, sz, u32, u32, vp],
+                                            ctypes.c_int),
+        "rss_key_byte_neighbourhood_weighted_device": ([key_p, u32, u32, vp, vp, sz, u32, u32, vp,
+                                                        vp], ctypes.c_int),
+        "rss_key_byte_neighbourhood_weighted_host": ([vp, key_p, u32, u32, vp, vp, sz, u32, u32,
+                                                      vp], ctypes.c_int),
+        "rss_key_byte_neighbourhood6_device": ([ctypes.POINTER(RssKey6), u32, u32, vp, sz, u32,
+                                                u32, vp, vp], ctypes.c_int),
+        "rss_key_byte_neighbourhood6_host": ([vp, ctypes.POINTER(RssKey6), u32, u32, vp, sz, u32,
+                                              u32, vp], ctypes.c_int),
         "rss_symmetric_key": ([ctypes.c_uint16, vp, sz], ctypes.c_int),
         "rss_symmetric_fold_device": ([vp, u32, u32, vp, sz, vp, u32, vp], ctypes.c_int),
         "rss_symmetric_search_device": ([vp, u32, u32, u32, u32, vp, vp], ctypes.c_int),
@@ -596,6 +613,44 @@ class HostContext:
                "rss_key_neighbourhood6_host")
         return out
 
+    def key_byte_neighbourhood(self, key, tuples, htable, nqueues, first_byte=0, nbytes=None,
+                               weights=None):
+        """Per-queue counts (uint64[nbytes * 256, min(htable, nqueues)]) of ``tuples`` under
+        every value of bytes ``[first_byte, first_byte + nbytes)`` (default: to byte 15) of the
+        prepared ``key`` (``rss_key_byte_neighbourhood_host``): row ``256 * (B - first_byte) +
+        v`` has byte B set to v, so row ``256 * (B - first_byte) + key[B]`` is the key's own.
+        With ``weights`` (one u32 per tuple) the rows are loads
+        (``rss_key_byte_neighbourhood_weighted_host``)."""
+        htable, nqueues = queue_modulus(htable, nqueues)
+        arr = np.ascontiguousarray(tuples)
+        if arr.dtype != TUPLE_DTYPE:
+            arr = np.ascontiguousarray(arr, dtype=np.uint32).reshape(-1, 3)
+        nbytes = KEY_BYTES - first_byte if nbytes is None else nbytes
+        out = np.zeros((max(nbytes, 0) * 256, nqueues), dtype=np.uint64)
+        if weights is not None:
+            w = tuple_weights(weights, len(arr))
+            _check(self._lib.rss_key_byte_neighbourhood_weighted_host(
+                self._ctx, ctypes.byref(key), first_byte, nbytes, arr.ctypes.data, w.ctypes.data,
+                len(arr), htable, nqueues, out.ctypes.data),
+                "rss_key_byte_neighbourhood_weighted_host")
+            return out
+        _check(self._lib.rss_key_byte_neighbourhood_host(
+            self._ctx, ctypes.byref(key), first_byte, nbytes, arr.ctypes.data, len(arr), htable,
+            nqueues, out.ctypes.data), "rss_key_byte_neighbourhood_host")
+        return out
+
+    def key_byte_neighbourhood6(self, key6, tuples, htable, nqueues, first_byte=0, nbytes=None):
+        """:meth:`key_byte_neighbourhood` for IPv6 (``rss_key_byte_neighbourhood6_host``): the
+        40 bytes of the key, ``nbytes`` defaulting to the bytes up to 39."""
+        htable, nqueues = queue_modulus(htable, nqueues)
+        arr = _tuples6(tuples)
+        nbytes = KEY6_BYTES - first_byte if nbytes is None else nbytes
+        out = np.zeros((max(nbytes, 0) * 256, nqueues), dtype=np.uint64)
+        _check(self._lib.rss_key_byte_neighbourhood6_host(
+            self._ctx, ctypes.byref(key6), first_byte, nbytes, arr.ctypes.data, len(arr), htable,
+            nqueues, out.ctypes.data), "rss_key_byte_neighbourhood6_host")
+        return out
+
 
     def symmetric_search(self, tuples, htable, nqueues, first_pattern=0,
                          npatterns=SYMMETRIC_PATTERNS, ipv6=False, weights=None,
@@ -863,6 +918,37 @@ def key_neighbourhood_weighted_device(key, tuples_ptr, weights_ptr, n, htable, n
     _check(load().rss_key_neighbourhood_weighted_device(ctypes.byref(key), tuples_ptr, weights_ptr,
                                                         n, htable, nqueues, loads_ptr, stream),
            "rss_key_neighbourhood_weighted_device")
+
+
+def key_byte_neighbourhood_device(key, first_byte, nbytes, tuples_ptr, n, htable, nqueues,
+                                  counts_ptr, stream=None):
+    """Stream-ordered ``rss_key_byte_neighbourhood_device`` on raw device pointers (ints);
+    ``counts_ptr``: uint64[nbytes * 256, min(htable, nqueues)], overwritten."""
+    htable, nqueues = queue_modulus(htable, nqueues)
+    _check(load().rss_key_byte_neighbourhood_device(
+        ctypes.byref(key), first_byte, nbytes, tuples_ptr, n, htable, nqueues, counts_ptr, stream),
+        "rss_key_byte_neighbourhood_device")
+
+
+def key_byte_neighbourhood6_device(key6, first_byte, nbytes, tuples_ptr, n, htable, nqueues,
+                                   counts_ptr, stream=None):
+    """Stream-ordered ``rss_key_byte_neighbourhood6_device`` on raw device pointers (ints);
+    ``counts_ptr``: uint64[nbytes * 256, min(htable, nqueues)], overwritten."""
+    htable, nqueues = queue_modulus(htable, nqueues)
+    _check(load().rss_key_byte_neighbourhood6_device(
+        ctypes.byref(key6), first_byte, nbytes, tuples_ptr, n, htable, nqueues, counts_ptr,
+        stream), "rss_key_byte_neighbourhood6_device")
+
+
+def key_byte_neighbourhood_weighted_device(key, first_byte, nbytes, tuples_ptr, weights_ptr, n,
+                                           htable, nqueues, loads_ptr, stream=None):
+    """Stream-ordered ``rss_key_byte_neighbourhood_weighted_device`` on raw device pointers
+    (ints): ``weights_ptr`` n uint32; ``loads_ptr``: uint64[nbytes * 256, min(htable,
+    nqueues)], overwritten."""
+    htable, nqueues = queue_modulus(htable, nqueues)
+    _check(load().rss_key_byte_neighbourhood_weighted_device(
+        ctypes.byref(key), first_byte, nbytes, tuples_ptr, weights_ptr, n, htable, nqueues,
+        loads_ptr, stream), "rss_key_byte_neighbourhood_weighted_device")
 
 
 def symmetric_fold_device(tuples_ptr, words, fields, weights_ptr, n, folds_ptr, flags=0,

@@ -1,6 +1,6 @@
 // rss_engine.h -- the engine's launchers (rss_toeplitz.hip, rss_keysearch.hip,
-// rss_keysearch6.hip, rss_neighbourhood.hip, rss_keysearch_weighted.hip, rss_symmetric.hip,
-// rss_flow_aggregate.hip) as the C ABI (rss_host.hip) calls
+// rss_keysearch6.hip, rss_neighbourhood.hip, rss_byte_neighbourhood.hip,
+// rss_keysearch_weighted.hip, rss_symmetric.hip, rss_flow_aggregate.hip) as the C ABI (rss_host.hip) calls
 // them, and the HIP error macro both use.  Internal, not ABI.
 #pragma once
 
@@ -59,6 +59,16 @@ RSS_HIDDEN int launch_neighbourhood_weighted(const rss_key* key, const rss_tuple
                                              const uint32_t* d_weights, size_t n, uint32_t htable,
                                              uint32_t nqueues, uint64_t* d_loads,
                                              hipStream_t stream);
+// rss_key_byte_neighbourhood_device / _weighted_device (d_weights non-NULL) / 6_device
+// (rss_byte_neighbourhood.hip; arguments validated by the caller)
+RSS_HIDDEN int launch_byte_neighbourhood(const rss_key* key, uint32_t first_byte, uint32_t nbytes,
+                                         const rss_tuple4* d_tuples, const uint32_t* d_weights,
+                                         size_t n, uint32_t htable, uint32_t nqueues,
+                                         uint64_t* d_counts, hipStream_t stream);
+RSS_HIDDEN int launch_byte_neighbourhood6(const rss_key6* key, uint32_t first_byte,
+                                          uint32_t nbytes, const rss_tuple6* d_tuples, size_t n,
+                                          uint32_t htable, uint32_t nqueues, uint64_t* d_counts,
+                                          hipStream_t stream);
 // rss_symmetric_fold_device / rss_symmetric_search_device (rss_symmetric.hip; arguments
 // validated by the caller)
 RSS_HIDDEN int launch_symmetric_fold(const void* d_tuples, uint32_t words, uint32_t fields,

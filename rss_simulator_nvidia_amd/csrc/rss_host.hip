@@ -110,6 +110,16 @@ int check_neighbourhood6(const char* who, const rss_key6* key, const rss_tuple6*
     return RSS_OK;
 }
 
+// the rss_key_byte_neighbourhood entries: bytes [first_byte, first_byte + nbytes) of the `limit`
+// a hash reads
+int check_byte_range(const char* who, uint32_t first_byte, uint32_t nbytes, uint32_t limit) {
+    if (nbytes == 0) return rss_set_error(RSS_EINVAL, "%s: nbytes is 0", who);
+    if ((uint64_t)first_byte + nbytes > limit)
+        return rss_set_error(RSS_EINVAL, "%s: bytes [%u, %llu) exceed the %u key bytes a hash reads",
+                             who, first_byte, (unsigned long long)first_byte + nbytes, limit);
+    return RSS_OK;
+}
+
 // rss_key_search6_device / _host, rss_key_search_weighted_device / _host
 int check_search6(const char* who, const char* what, const void* windows_or_keys, size_t nkeys,
                   const void* tuples, size_t n, uint32_t htable, uint32_t nqueues,
@@ -420,6 +430,45 @@ int rss_key_neighbourhood_weighted_device(const rss_key* key, const rss_tuple4* 
                                               static_cast<hipStream_t>(stream));
 }
 
+int rss_key_byte_neighbourhood_device(const rss_key* key, uint32_t first_byte, uint32_t nbytes,
+                                      const rss_tuple4* d_tuples, size_t n, uint32_t htable,
+                                      uint32_t nqueues, uint64_t* d_counts, void* stream) {
+    const char* who = "rss_key_byte_neighbourhood_device";
+    int rc = check_neighbourhood(who, key, d_tuples, n, htable, nqueues, d_counts);
+    if (rc == RSS_OK) rc = check_byte_range(who, first_byte, nbytes, RSS_KEY_BYTES);
+    if (rc) return rc;
+    return rss::launch_byte_neighbourhood(key, first_byte, nbytes, d_tuples, nullptr, n, htable,
+                                          nqueues, d_counts, static_cast<hipStream_t>(stream));
+}
+
+int rss_key_byte_neighbourhood6_device(const rss_key6* key, uint32_t first_byte, uint32_t nbytes,
+                                       const rss_tuple6* d_tuples, size_t n, uint32_t htable,
+                                       uint32_t nqueues, uint64_t* d_counts, void* stream) {
+    const char* who = "rss_key_byte_neighbourhood6_device";
+    int rc = check_neighbourhood6(who, key, d_tuples, n, htable, nqueues, d_counts);
+    if (rc == RSS_OK) rc = check_byte_range(who, first_byte, nbytes, RSS_KEY6_BYTES);
+    if (rc) return rc;
+    return rss::launch_byte_neighbourhood6(key, first_byte, nbytes, d_tuples, n, htable, nqueues,
+                                           d_counts, static_cast<hipStream_t>(stream));
+}
+
+int rss_key_byte_neighbourhood_weighted_device(const rss_key* key, uint32_t first_byte,
+                                               uint32_t nbytes, const rss_tuple4* d_tuples,
+                                               const uint32_t* d_weights, size_t n,
+                                               uint32_t htable, uint32_t nqueues,
+                                               uint64_t* d_loads, void* stream) {
+    const char* who = "rss_key_byte_neighbourhood_weighted_device";
+    int rc = check_neighbourhood(who, key, d_tuples, n, htable, nqueues, d_loads);
+    if (rc == RSS_OK) rc = check_weights(who, d_weights, n);
+    if (rc == RSS_OK) rc = check_byte_range(who, first_byte, nbytes, RSS_KEY_BYTES);
+    if (rc) return rc;
+    if (n == 0)  // no weights to tell the launcher by: the unweighted launch only clears
+        return rss::launch_byte_neighbourhood(key, first_byte, nbytes, d_tuples, nullptr, 0, htable,
+                                              nqueues, d_loads, static_cast<hipStream_t>(stream));
+    return rss::launch_byte_neighbourhood(key, first_byte, nbytes, d_tuples, d_weights, n, htable,
+                                          nqueues, d_loads, static_cast<hipStream_t>(stream));
+}
+
 int rss_symmetric_key(uint16_t pattern, uint8_t* key, size_t len) {
     if (!key) return rss_set_error(RSS_EINVAL, "rss_symmetric_key: key is NULL");
     if (len % 2 || len < RSS_KEY_MIN_BYTES || len > RSS_KEY_MAX_BYTES)
@@ -532,6 +581,26 @@ int rss_ctx_create(int device, rss_ctx** out) {
     }
     *out = ctx;
     return RSS_OK;
+}
+
+int rss_key_byte_neighbourhood6_host(rss_ctx* ctx, const rss_key6* key, uint32_t first_byte,
+                                     uint32_t nbytes, const rss_tuple6* h_tuples, size_t n,
+                                     uint32_t htable, uint32_t nqueues, uint64_t* h_counts) {
+    const char* who = "rss_key_byte_neighbourhood6_host";
+    int rc = check_neighbourhood6(who, key, h_tuples, n, htable, nqueues, h_counts);
+    if (rc == RSS_OK) rc = check_byte_range(who, first_byte, nbytes, RSS_KEY6_BYTES);
+    if (rc) return rc;
+    if (!ctx) return rss_set_error(RSS_EINVAL, "%s: context is NULL", who);
+    const size_t count_bytes = sizeof(uint64_t) * 256 * nbytes * nqueues;
+    if (n == 0) {
+        memset(h_counts, 0, count_bytes);
+        return RSS_OK;
+    }
+    return key_host_run(who, ctx, {}, h_tuples, n, count_bytes, h_counts,
+                        [&](uint32_t*, rss_tuple6* d_t, uint32_t*, uint64_t* d_c, hipStream_t s) {
+                            return rss::launch_byte_neighbourhood6(key, first_byte, nbytes, d_t, n,
+                                                                   htable, nqueues, d_c, s);
+                        });
 }
 
 }  // extern "C"
@@ -970,6 +1039,50 @@ int rss_key_neighbourhood_weighted_host(rss_ctx* ctx, const rss_key* key,
                             hipStream_t s) {
                             return rss::launch_neighbourhood_weighted(key, d_t, d_wt, n, htable,
                                                                       nqueues, d_c, s);
+                        }, h_weights);
+}
+
+int rss_key_byte_neighbourhood_host(rss_ctx* ctx, const rss_key* key, uint32_t first_byte,
+                                    uint32_t nbytes, const rss_tuple4* h_tuples, size_t n,
+                                    uint32_t htable, uint32_t nqueues, uint64_t* h_counts) {
+    const char* who = "rss_key_byte_neighbourhood_host";
+    int rc = check_neighbourhood(who, key, h_tuples, n, htable, nqueues, h_counts);
+    if (rc == RSS_OK) rc = check_byte_range(who, first_byte, nbytes, RSS_KEY_BYTES);
+    if (rc) return rc;
+    if (!ctx) return rss_set_error(RSS_EINVAL, "%s: context is NULL", who);
+    const size_t count_bytes = sizeof(uint64_t) * 256 * nbytes * nqueues;
+    if (n == 0) {
+        memset(h_counts, 0, count_bytes);
+        return RSS_OK;
+    }
+    return key_host_run(who, ctx, {}, h_tuples, n, count_bytes, h_counts,
+                        [&](uint32_t*, rss_tuple4* d_t, uint32_t*, uint64_t* d_c, hipStream_t s) {
+                            return rss::launch_byte_neighbourhood(key, first_byte, nbytes, d_t,
+                                                                  nullptr, n, htable, nqueues, d_c, s);
+                        });
+}
+
+int rss_key_byte_neighbourhood_weighted_host(rss_ctx* ctx, const rss_key* key,
+                                             uint32_t first_byte, uint32_t nbytes,
+                                             const rss_tuple4* h_tuples,
+                                             const uint32_t* h_weights, size_t n, uint32_t htable,
+                                             uint32_t nqueues, uint64_t* h_loads) {
+    const char* who = "rss_key_byte_neighbourhood_weighted_host";
+    int rc = check_neighbourhood(who, key, h_tuples, n, htable, nqueues, h_loads);
+    if (rc == RSS_OK) rc = check_weights(who, h_weights, n);
+    if (rc == RSS_OK) rc = check_byte_range(who, first_byte, nbytes, RSS_KEY_BYTES);
+    if (rc) return rc;
+    if (!ctx) return rss_set_error(RSS_EINVAL, "%s: context is NULL", who);
+    const size_t load_bytes = sizeof(uint64_t) * 256 * nbytes * nqueues;
+    if (n == 0) {
+        memset(h_loads, 0, load_bytes);
+        return RSS_OK;
+    }
+    return key_host_run(who, ctx, {}, h_tuples, n, load_bytes, h_loads,
+                        [&](uint32_t*, rss_tuple4* d_t, uint32_t* d_wt, uint64_t* d_c,
+                            hipStream_t s) {
+                            return rss::launch_byte_neighbourhood(key, first_byte, nbytes, d_t, d_wt,
+                                                                  n, htable, nqueues, d_c, s);
                         }, h_weights);
 }
 

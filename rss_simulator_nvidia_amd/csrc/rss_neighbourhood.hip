@@ -53,56 +53,6 @@ namespace {
 //     queues up to        38    76    152   304   608   1217
 // then [queue][neighbour] bins with ng = 16 up to 2434 queues, 8 to 4868, 4 to 9736, 2 to 19472,
 // 1 to 38944, then global atomics.
-constexpr int kWords6 = RSS_INPUT6_BITS / 32;                                     // 9
-template <int kWords>
-constexpr uint32_t kNbrLutDwords = kWords * kSmallFields * 32;                    // 672 / 2016
-constexpr uint32_t kNbr6BinBytesMax = kLdsBytes - kNbrLutDwords<kWords6> * 4;     // 155776
-static_assert(kNbrLutDwords<3> == kSmallLutDwords && kNbr6BinBytesMax == 155776, "table sizes");
-
-// IPv6: the same span from nine words.  With x[-1] = x[9] = x[10] = 0, R's word k is
-// alignbit(x[k], x[k - 1], 1) for every k = 0 .. 10, so the span's two words need x[word - 1],
-// x[word], x[word + 1] -- a uniform pick among the lane's nine registers (27 v_cndmask_b32).
-__device__ __forceinline__ uint2 flip_span6(const uint32_t* w, uint32_t word, uint32_t s0) {
-    // selects on scalar conditions (a switch would turn into indexing and put w[] in scratch)
-    uint32_t a = 0u, b = 0u, c = 0u;  // tuple words word - 1, word, word + 1 (0 outside the tuple)
-#pragma unroll
-    for (uint32_t k = 0; k < (uint32_t)kWords6; ++k) {
-        a = word == k + 1 ? w[k] : a;
-        b = word == k ? w[k] : b;
-        c = word + 1 == k ? w[k] : c;
-    }
-    const uint32_t xa = __brev(a), xb = __brev(b), xc = __brev(c);
-    const uint32_t lo = alignbit(xb, xa, 1), hi = alignbit(xc, xb, 1);
-    return make_uint2(alignbit(hi, lo, s0), hi >> s0);
-}
-
-// the 63 IPv6 small tables from the key's ten words (key bits [32 k, 32 k + 32) in kw[k], bit
-// 319 unused): window i = key bits [i, i + 32)
-__device__ __forceinline__ void build_small_lut6(uint32_t* lut, const uint32_t* __restrict__ kw,
-                                                 uint32_t tid) {
-    for (uint32_t e = tid; e < kNbrLutDwords<kWords6>; e += kBlock) {
-        const int t = (int)(e >> 5);
-        const uint32_t v = e & 31u;
-        const int width = small_width(t % kSmallFields);
-        uint32_t x = 0;
-#pragma unroll
-        for (int b = 0; b < 5; ++b) {
-            const uint32_t i = (uint32_t)small_slice_bit(t, b);  // < 288
-            const uint64_t two = (uint64_t)kw[i >> 5] << 32 | kw[(i >> 5) + 1];
-            x ^= (b < width && ((v >> b) & 1u)) ? (uint32_t)((two << (i & 31u)) >> 32) : 0u;
-        }
-        lut[e] = (v >> width) ? 0u : x;
-    }
-}
-
-__device__ __forceinline__ uint32_t toeplitz_hash_small6(const uint32_t* __restrict__ lut,
-                                                         const uint32_t* w) {
-    const char* b = reinterpret_cast<const char*>(lut);
-    return xor3(xor3(small_word<0>(b, w[0]), small_word<7>(b, w[1]), small_word<14>(b, w[2])),
-                xor3(small_word<21>(b, w[3]), small_word<28>(b, w[4]), small_word<35>(b, w[5])),
-                xor3(small_word<42>(b, w[6]), small_word<49>(b, w[7]), small_word<56>(b, w[8])));
-}
-
 template <int kWords, int kNG, bool kHPow2, int kQMode, int kHist>
 __global__ __launch_bounds__(kBlock) void rss_key_neighbourhood_kernel(const LaunchParams p) {
     __shared__ uint32_t lut[kNbrLutDwords<kWords>];

@@ -14,7 +14,9 @@ of the H buckets, so a perfect key gives it ``n * slots(q) / H`` flows.
 ``--refine STEPS`` then improves the best candidate (and a ``--key-file`` key) by local
 search: Toeplitz is linear in the key, so all 128 single-bit flips of a key are scored in
 one launch from the key's own hashes (``rss_key_neighbourhood_device``), and :func:`refine`
-flips the best bit until none improves the spread.
+flips the best bit until none improves the spread.  ``--refine-step byte`` descends over whole
+bytes instead: every value of every key byte in one launch (``rss_key_byte_neighbourhood_device``;
+a byte's 256 values contain its 8 single-bit flips), as NIC keys are programmed.
 
 ``--ipv6`` does the same for a CSV of IPv6 flows (``rss_key_search6_device``,
 ``rss_key_neighbourhood6_device``: 36-byte tuples, the 320 key bits an IPv6 hash reads).
@@ -241,8 +243,93 @@ def _resident_neighbourhood(tuples, htable, nqueues, ipv6=False, weights=None):
     return score
 
 
+def _byte_range(bytes, ipv6):
+    total = _native.KEY6_BYTES if ipv6 else _native.KEY_BYTES
+    if bytes is None:
+        return 0, total
+    if isinstance(bytes, range):
+        if bytes.step != 1:
+            raise ValueError("bytes must be consecutive, got %r" % (bytes,))
+        return bytes.start, len(bytes)
+    first, count = bytes
+    return int(first), int(count)
+
+
+def byte_neighbourhood(key, tuples, htable, nqueues, bytes=None, ctx=None, ipv6=False,
+                       weights=None):
+    """uint64 counts ``[nbytes * 256, min(H, Q)]`` of packed ``tuples`` under every value of
+    every key byte in ``bytes`` (a ``range`` with step 1 or ``(first, count)``; default all 16,
+    ``ipv6``: 40) -- GPU, one launch: row ``256 * (B - first) + v`` = ``key`` with byte B set
+    to v, so row ``256 * (B - first) + key[B]`` is ``key`` itself.  ``weights`` (IPv4 only):
+    the rows are loads, the sums of the tuples' weights."""
+    _no_ipv6_weights(ipv6, weights)
+    first, count = _byte_range(bytes, ipv6)
+    ctx = ctx or _native.default_context()
+    if ipv6:
+        return ctx.key_byte_neighbourhood6(_native.prepare_key6(key), tuples, htable, nqueues,
+                                           first, count)
+    return ctx.key_byte_neighbourhood(_native.prepare_key(key), tuples, htable, nqueues, first,
+                                      count, weights)
+
+
+def _resident_byte_neighbourhood(tuples, htable, nqueues, ipv6=False, weights=None):
+    """``key -> counts[16 * 256, min(H, Q)]`` (``ipv6``: 40 * 256 rows) on tuples -- and
+    ``weights`` -- uploaded once: one ``rss_key_byte_neighbourhood_device`` / ``..6_device`` /
+    ``.._weighted_device`` launch per call."""
+    _no_ipv6_weights(ipv6, weights)
+    import torch
+    arr = np.ascontiguousarray(tuples)
+    if arr.dtype != (_native.TUPLE6_DTYPE if ipv6 else _native.TUPLE_DTYPE):
+        arr = np.ascontiguousarray(arr, dtype=np.uint32).reshape(-1, 9 if ipv6 else 3)
+    n = len(arr)
+    dev = torch.device("cuda:%d" % _native.default_context().device)
+    d_tuples = torch.from_numpy(np.ascontiguousarray(arr).view(np.int32).reshape(-1)).to(dev)
+    if weights is not None:
+        d_weights = torch.from_numpy(_native.tuple_weights(weights, n).view(np.int32)).to(dev)
+    width = _native.queue_modulus(htable, nqueues)[1]
+    nbytes = _native.KEY6_BYTES if ipv6 else _native.KEY_BYTES
+    d_counts = torch.empty((nbytes * 256, width), dtype=torch.int64, device=dev)
+
+    def score(key):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if ipv6:
+            _native.key_byte_neighbourhood6_device(
+                _native.prepare_key6(key), 0, nbytes, d_tuples.data_ptr(), n, htable, nqueues,
+                d_counts.data_ptr(), stream)
+        elif weights is not None:
+            _native.key_byte_neighbourhood_weighted_device(
+                _native.prepare_key(key), 0, nbytes, d_tuples.data_ptr(), d_weights.data_ptr(), n,
+                htable, nqueues, d_counts.data_ptr(), stream)
+        else:
+            _native.key_byte_neighbourhood_device(
+                _native.prepare_key(key), 0, nbytes, d_tuples.data_ptr(), n, htable, nqueues,
+                d_counts.data_ptr(), stream)
+        return d_counts.cpu().numpy().view(np.uint64)
+
+    return score
+
+
+def _refine_bytes(key, score, htable, nqueues, max_steps):
+    """:func:`refine` with ``step="byte"``: coordinate descent over the key's bytes."""
+    moves = []
+    counts = np.asarray(score(key))
+    while True:
+        own = key[0]  # row 256 * 0 + key[0]: the key's own counts
+        m = balance(counts, htable, nqueues)
+        best = int(np.lexsort((m["chi2"], m["max_load"]))[0])
+        better = (m["max_load"][best], m["chi2"][best]) < (m["max_load"][own], m["chi2"][own])
+        if not better or len(moves) >= max_steps:
+            return {"key": key, "max_load": float(m["max_load"][own]), "chi2": float(m["chi2"][own]),
+                    "used": int(m["used"][own]), "counts": counts[own].copy(), "flips": [],
+                    "moves": moves}
+        key = list(key)
+        key[best >> 8] = best & 0xFF
+        moves.append((best >> 8, best & 0xFF))
+        counts = np.asarray(score(key))
+
+
 def refine(key, tuples, htable, nqueues, max_steps=64, neighbourhood=None, ipv6=False,
-           weights=None):
+           weights=None, step="bit"):
     """Hill-climb ``key`` over single-bit flips (steepest descent on ``(max_load, chi2)``).
 
     Each step scores the key's 128 neighbours (``ipv6``: 320; one
@@ -254,9 +341,23 @@ def refine(key, tuples, htable, nqueues, max_steps=64, neighbourhood=None, ipv6=
     ``chi2``, ``used``, ``counts`` (of the returned key) and ``flips`` (the bits, in order).
     With ``weights`` (IPv4 only; uploaded once beside the tuples,
     ``rss_key_neighbourhood_weighted_device``) the climb is on per-queue loads.
+
+    ``step="byte"`` descends over whole bytes instead: each step scores every value of every
+    key byte (16 * 256 rows, ``ipv6``: 40 * 256; one ``rss_key_byte_neighbourhood_device`` /
+    ``..6_device`` / ``.._weighted_device`` launch, or ``neighbourhood(key)`` returning those
+    rows) and sets the byte of the smallest ``(max_load, chi2)`` row while that is strictly
+    below the key's own (row ``key[0]``).  A byte's values contain its single-bit flips, so one
+    byte step is never worse than one bit step.  The dict then holds ``moves``, the ``(byte,
+    value)`` pairs in order, and an empty ``flips``.
     """
     _no_ipv6_weights(ipv6, weights)
+    if step not in ("bit", "byte"):
+        raise ValueError("step must be 'bit' or 'byte', got %r" % (step,))
     key = [int(b) for b in key]
+    if step == "byte":
+        score = neighbourhood or _resident_byte_neighbourhood(tuples, htable, nqueues, ipv6,
+                                                              weights)
+        return _refine_bytes(key, score, htable, nqueues, max_steps)
     score = neighbourhood or _resident_neighbourhood(tuples, htable, nqueues, ipv6, weights)
     flips = []
     counts = np.asarray(score(key))
@@ -337,6 +438,10 @@ def main(argv=None):
     p.add_argument("--refine", metavar="STEPS", type=int, default=0,
                    help="then hill-climb the top-ranked key (and the --key-file key) over "
                         "single-bit flips, at most STEPS flips each")
+    p.add_argument("--refine-step", choices=("bit", "byte"), default="bit",
+                   help="what one --refine step changes: the best single bit (default), or the "
+                        "best value of any one key byte (every value of every byte is scored per "
+                        "step)")
     p.add_argument("--out", metavar="PATH", help="write the best key in --key-file format")
     p.add_argument("--ipv6", action="store_true",
                    help="the file holds IPv6 flows (36-byte hash input, 320 key bits)")
@@ -354,6 +459,9 @@ def main(argv=None):
                 "are always folded to flows")
     if args.symmetric and args.refine > 0:
         p.error("--refine cannot be combined with --symmetric: a single-bit flip breaks the "
+                "key's symmetry")
+    if args.symmetric and args.refine_step != "bit":
+        p.error("--refine-step cannot be combined with --symmetric: a changed byte breaks the "
                 "key's symmetry")
     if args.refine > 0:
         # refine keeps its tuples in torch tensors: torch opens the device before the
@@ -405,10 +513,11 @@ def main(argv=None):
               % (key_text(r["key"]), r["max_load"], r["chi2"], r["used"]))
     if args.refine > 0:
         starts = [ranked[0]["key"]] + extra
-        score = _resident_neighbourhood(tuples, args.htable_size, args.num_queues, args.ipv6,
-                                        weights)
-        refined = [refine(k, tuples, args.htable_size, args.num_queues, args.refine, score)
-                   for k in starts]
+        resident = (_resident_byte_neighbourhood if args.refine_step == "byte"
+                    else _resident_neighbourhood)
+        score = resident(tuples, args.htable_size, args.num_queues, args.ipv6, weights)
+        refined = [refine(k, tuples, args.htable_size, args.num_queues, args.refine, score,
+                          step=args.refine_step) for k in starts]
         refined.sort(key=lambda r: (r["max_load"], r["chi2"]))
         for r in refined:
             print("%s  max_load %.4f chi2 %.2f queues used %d"
