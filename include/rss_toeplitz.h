@@ -269,6 +269,41 @@ int rss_key_neighbourhood_weighted_device(const rss_key* key, const rss_tuple4* 
                                           uint32_t nqueues, uint64_t* d_loads, void* stream);
 
 /*
+ * Key search over time: the load each key puts on each queue in each time window of a packet
+ * stream -- what a total per queue cannot show: two heavy flows on one queue in the same
+ * second.  One row per packet: d_tuples[i], its weight d_weights[i] (n uint32, or NULL for 1
+ * per packet) and its window d_slots[i] (n uint32).  d_loads: nkeys x nslots x nqueues uint64,
+ * overwritten: d_loads[k][s][q] is the exact sum of the weights of the packets with slot == s
+ * and hash_k % htable % nqueues == q.  A packet whose slot is >= nslots is counted nowhere;
+ * columns [min(htable, nqueues), nqueues) are zero.  Exact for any u32 weights, any htable,
+ * nqueues >= 1, any n, any 4-byte aligned pointers and any order of the slots.  Time order is
+ * what makes it fast: a workgroup walks one contiguous tile of packets and keeps 64-bit LDS
+ * bins for the slots [s, s + S) from its first packet's slot s on; a packet outside them is one
+ * global 64-bit atomic per key.  With q = min(htable, nqueues) and S = the slots whose bins fit:
+ *   power-of-two htable <= 65536 (158464 B of bins; lane-private rows of 256 B)
+ *     8 keys per workgroup (htable <= 256)  q <= 38     (S = 3 at q = 24)
+ *     4 keys                                q <= 77     (S = 6 at q = 24)
+ *     2 keys                                q <= 154
+ *     4 keys, shared bins of 8 B            q <= 2476
+ *   any other htable (40960 B of bins, 2 keys per workgroup)
+ *     lane-private rows                     q <= 40
+ *     shared bins                           q <= 1280
+ *   past those one global atomic per (packet, key).
+ * Keys per workgroup are halved until S >= 2, and while half would still hold all nkeys.
+ * Tuples, slots and (if given) weights all 16-byte aligned take the 4-packets-per-lane path.
+ * The loads are cleared by a kernel of the same call (n == 0 only clears), so the entry can be
+ * captured into a graph.
+ * RSS_EINVAL, before any device work, with rss_last_error naming the entry and the cause:
+ * windows, loads or slots NULL; nkeys == 0; nslots == 0; n > 0 with tuples NULL; htable or
+ * nqueues 0.  IPv6 tuples are out of scope.
+ */
+int rss_key_search_timeline_device(const uint32_t* d_windows, size_t nkeys,
+                                   const rss_tuple4* d_tuples, const uint32_t* d_weights,
+                                   const uint32_t* d_slots, size_t n, uint32_t nslots,
+                                   uint32_t htable, uint32_t nqueues, uint64_t* d_loads,
+                                   void* stream);
+
+/*
  * Symmetric RSS: rank the keys that hash both directions of a connection to one queue.  A key
  * with a 16-bit period (DPDK's 6d:5a:6d:5a:... is pattern 0x6d5a) has window[i] depending only
  * on i % 16, so a tuple's hash depends only on f, the XOR of its 16-bit half-words: with f_r =
@@ -638,6 +673,16 @@ int rss_key_neighbourhood_weighted_host(rss_ctx* ctx, const rss_key* key,
                                         const rss_tuple4* h_tuples, const uint32_t* h_weights,
                                         size_t n, uint32_t htable, uint32_t nqueues,
                                         uint64_t* h_loads);
+
+/* rss_key_search_timeline_device on host buffers (keys: nkeys prepared keys; h_weights: n
+ * uint32 or NULL; h_slots: n uint32; h_loads: nkeys x nslots x nqueues uint64), as
+ * rss_key_search_weighted_host: takes the context's lock, uploads, launches, copies the loads
+ * back.  Synchronous.  The same validation (and a NULL ctx, or a key that was not prepared) is
+ * refused first; n == 0 zeroes h_loads on the host. */
+int rss_key_search_timeline_host(rss_ctx* ctx, const rss_key* keys, size_t nkeys,
+                                 const rss_tuple4* h_tuples, const uint32_t* h_weights,
+                                 const uint32_t* h_slots, size_t n, uint32_t nslots,
+                                 uint32_t htable, uint32_t nqueues, uint64_t* h_loads);
 
 /* rss_symmetric_fold_device + rss_symmetric_search_device on host buffers (described with
  * them): h_tuples n x `words` uint32, h_weights n uint32 or NULL, h_loads npatterns x nqueues

@@ -50,6 +50,7 @@ EXPORTED_SYMBOLS = (
     "rss_key_byte_neighbourhood_device", "rss_key_byte_neighbourhood6_device",
     "rss_key_byte_neighbourhood_weighted_device", "rss_key_byte_neighbourhood_host",
     "rss_key_byte_neighbourhood6_host", "rss_key_byte_neighbourhood_weighted_host",
+    "rss_key_search_timeline_device", "rss_key_search_timeline_host",
 )
 SYMMETRIC_PATTERNS = 65536  # RSS_SYMMETRIC_PATTERNS: 16-bit key patterns = fold values
 KEY_NEIGHBOURS = 128  # RSS_KEY_NEIGHBOURS: the key bits an IPv4 hash reads
@@ -126,6 +127,10 @@ def _bind(lib):
         "rss_key_search_weighted_host": ([vp, vp, sz, vp, vp, sz, u32, u32, vp], ctypes.c_int),
         "rss_key_neighbourhood_weighted_host": ([vp, key_p, vp, vp, sz, u32, u32, vp],
                                                 ctypes.c_int),
+        "rss_key_search_timeline_device": ([vp, sz, vp, vp, vp, sz, u32, u32, u32, vp, vp],
+                                           ctypes.c_int),
+        "rss_key_search_timeline_host": ([vp, vp, sz, vp, vp, vp, sz, u32, u32, u32, vp],
+                                         ctypes.c_int),
         "rss_key_byte_neighbourhood_device": ([key_p, u32, u32, vp, sz, u32, u32, vp, vp],
                                               ctypes.c_int),
         "rss_key_byte_neighbourhood_host": ([vp, key_p, u32, u32, vp, sz, u32, u32, vp],
@@ -567,6 +572,25 @@ class HostContext:
                "rss_key_search_host")
         return out
 
+    def key_search_timeline(self, keys, tuples, slots, nslots, htable, nqueues, weights=None):
+        """Per-window, per-queue loads (uint64[len(keys), nslots, min(htable, nqueues)]) of the
+        packets ``tuples`` under each prepared key (``rss_key_search_timeline_host``): packet i
+        adds ``weights[i]`` (1 without ``weights``) to window ``slots[i]``; a packet whose slot
+        is ``>= nslots`` is counted nowhere."""
+        htable, nqueues = queue_modulus(htable, nqueues)
+        arr = np.ascontiguousarray(tuples)
+        if arr.dtype != TUPLE_DTYPE:
+            arr = np.ascontiguousarray(arr, dtype=np.uint32).reshape(-1, 3)
+        s = tuple_slots(slots, len(arr))
+        w = None if weights is None else tuple_weights(weights, len(arr))
+        karr = (RssKey * len(keys))(*keys)
+        out = np.zeros((len(keys), int(nslots), nqueues), dtype=np.uint64)
+        _check(self._lib.rss_key_search_timeline_host(
+            self._ctx, karr, len(keys), arr.ctypes.data, None if w is None else w.ctypes.data,
+            s.ctypes.data, len(arr), int(nslots), htable, nqueues, out.ctypes.data),
+            "rss_key_search_timeline_host")
+        return out
+
     def key_neighbourhood(self, key, tuples, htable, nqueues, weights=None):
         """Per-queue counts (uint64[128, min(htable, nqueues)]) of ``tuples`` under each
         single-bit flip of the prepared ``key`` (``rss_key_neighbourhood_host``): row j has
@@ -715,6 +739,19 @@ def tuple_weights(weights, n):
     if len(w) and (w.min() < 0 or w.max() > 0xFFFFFFFF):
         raise ValueError("weights must lie in [0, 2^32)")
     return np.ascontiguousarray(w, dtype=np.uint32)
+
+
+def tuple_slots(slots, n):
+    """``slots`` as contiguous uint32[n] for the timeline entry: one time window in [0, 2^32)
+    per packet, anything else is a ``ValueError``."""
+    s = np.asarray(slots)
+    if s.ndim != 1 or len(s) != n:
+        raise ValueError("slots: expected one slot per packet (%d), got shape %s" % (n, s.shape))
+    if s.dtype.kind not in "iu":
+        raise ValueError("slots must be integers, not %s" % s.dtype)
+    if len(s) and (s.min() < 0 or s.max() > 0xFFFFFFFF):
+        raise ValueError("slots must lie in [0, 2^32)")
+    return np.ascontiguousarray(s, dtype=np.uint32)
 
 
 def _tuples6(tuples):
@@ -908,6 +945,17 @@ def key_search_weighted_device(windows_ptr, nkeys, tuples_ptr, weights_ptr, n, h
     _check(load().rss_key_search_weighted_device(windows_ptr, nkeys, tuples_ptr, weights_ptr, n,
                                                  htable, nqueues, loads_ptr, stream),
            "rss_key_search_weighted_device")
+
+
+def key_search_timeline_device(windows_ptr, nkeys, tuples_ptr, weights_ptr, slots_ptr, n, nslots,
+                               htable, nqueues, loads_ptr, stream=None):
+    """Stream-ordered ``rss_key_search_timeline_device`` on raw device pointers (ints):
+    ``weights_ptr`` (n uint32, or None for 1 per packet) and ``slots_ptr`` (n uint32) beside
+    the tuples, ``loads_ptr`` = uint64[nkeys, nslots, nqueues] (overwritten)."""
+    _check(load().rss_key_search_timeline_device(windows_ptr, nkeys, tuples_ptr, weights_ptr,
+                                                 slots_ptr, n, nslots, htable, nqueues, loads_ptr,
+                                                 stream),
+           "rss_key_search_timeline_device")
 
 
 def key_neighbourhood_weighted_device(key, tuples_ptr, weights_ptr, n, htable, nqueues, loads_ptr,

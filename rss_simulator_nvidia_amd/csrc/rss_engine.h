@@ -1,6 +1,6 @@
 // rss_engine.h -- the engine's launchers (rss_toeplitz.hip, rss_keysearch.hip,
 // rss_keysearch6.hip, rss_neighbourhood.hip, rss_byte_neighbourhood.hip,
-// rss_keysearch_weighted.hip, rss_symmetric.hip, rss_flow_aggregate.hip) as the C ABI (rss_host.hip) calls
+// rss_keysearch_weighted.hip, rss_timeline.hip, rss_symmetric.hip, rss_flow_aggregate.hip) as the C ABI (rss_host.hip) calls
 // them, and the HIP error macro both use.  Internal, not ABI.
 #pragma once
 
@@ -59,6 +59,13 @@ RSS_HIDDEN int launch_neighbourhood_weighted(const rss_key* key, const rss_tuple
                                              const uint32_t* d_weights, size_t n, uint32_t htable,
                                              uint32_t nqueues, uint64_t* d_loads,
                                              hipStream_t stream);
+// rss_key_search_timeline_device (rss_timeline.hip; arguments validated by the caller;
+// d_weights may be NULL)
+RSS_HIDDEN int launch_search_timeline(const uint32_t* d_windows, size_t nkeys,
+                                      const rss_tuple4* d_tuples, const uint32_t* d_weights,
+                                      const uint32_t* d_slots, size_t n, uint32_t nslots,
+                                      uint32_t htable, uint32_t nqueues, uint64_t* d_loads,
+                                      hipStream_t stream);
 // rss_key_byte_neighbourhood_device / _weighted_device (d_weights non-NULL) / 6_device
 // (rss_byte_neighbourhood.hip; arguments validated by the caller)
 RSS_HIDDEN int launch_byte_neighbourhood(const rss_key* key, uint32_t first_byte, uint32_t nbytes,

@@ -140,6 +140,22 @@ int check_weights(const char* who, const uint32_t* weights, size_t n) {
     return RSS_OK;
 }
 
+// rss_key_search_timeline_device / _host
+int check_timeline(const char* who, const char* what, const void* windows_or_keys, size_t nkeys,
+                   const void* tuples, const uint32_t* slots, size_t n, uint32_t nslots,
+                   uint32_t htable, uint32_t nqueues, const uint64_t* loads) {
+    if (!windows_or_keys || !loads)
+        return rss_set_error(RSS_EINVAL, "%s: %s or loads is NULL", who, what);
+    if (!slots) return rss_set_error(RSS_EINVAL, "%s: slots is NULL", who);
+    if (nkeys == 0) return rss_set_error(RSS_EINVAL, "%s: no keys", who);
+    if (nslots == 0) return rss_set_error(RSS_EINVAL, "%s: no slots", who);
+    if (n && !tuples) return rss_set_error(RSS_EINVAL, "%s: tuples is NULL", who);
+    if (htable < 1 || nqueues < 1)
+        return rss_set_error(RSS_EINVAL, "%s: htable (%u) and nqueues (%u) must be >= 1", who,
+                             htable, nqueues);
+    return RSS_OK;
+}
+
 // rss_symmetric_fold_device / rss_symmetric_search_host: the flow set
 int check_symmetric_fold(const char* who, const void* tuples, uint32_t words, uint32_t fields,
                          size_t n) {
@@ -182,16 +198,19 @@ int check_flow_aggregate(const char* who, const void* tuples, uint32_t words, si
 // context's lock upload `windows` (search only; empty otherwise), the tuples and their weights
 // (weighted only; NULL otherwise), `launch(d_windows, d_tuples, d_weights, d_counts, stream)`,
 // copy count_bytes of counts back.  `scratch_bytes` more device bytes follow the counts (the
-// symmetric search's folds).  Synchronous.
+// symmetric search's folds).  `h_extra` (the timeline's slots; NULL otherwise): n more uint32
+// uploaded, their device copy in *d_extra before `launch` runs.  Synchronous.
 template <typename Tuple, typename Launch>
 int key_host_run(const char* who, rss_ctx* ctx, const std::vector<uint32_t>& windows,
                  const Tuple* h_tuples, size_t n, size_t count_bytes, uint64_t* h_counts,
-                 Launch launch, const uint32_t* h_weights = nullptr, size_t scratch_bytes = 0) {
+                 Launch launch, const uint32_t* h_weights = nullptr, size_t scratch_bytes = 0,
+                 const uint32_t* h_extra = nullptr, uint32_t** d_extra = nullptr) {
     std::lock_guard<std::mutex> lock(ctx->mu);  // (struct rss_ctx)
     RSS_HIP_CHECK(hipSetDevice(ctx->device));
     uint32_t* d_w = nullptr;
     Tuple* d_t = nullptr;
     uint32_t* d_wt = nullptr;
+    uint32_t* d_x = nullptr;
     uint64_t* d_c = nullptr;
     hipStream_t s = ctx->stream[0];
     auto cleanup = [&] {
@@ -199,6 +218,7 @@ int key_host_run(const char* who, rss_ctx* ctx, const std::vector<uint32_t>& win
         (void)hipFree(d_w);
         (void)hipFree(d_t);
         (void)hipFree(d_wt);
+        (void)hipFree(d_x);
         (void)hipFree(d_c);
     };
     const size_t window_bytes = windows.size() * sizeof(uint32_t);
@@ -206,6 +226,7 @@ int key_host_run(const char* who, rss_ctx* ctx, const std::vector<uint32_t>& win
     if (window_bytes) e = hipMalloc(&d_w, window_bytes);
     if (e == hipSuccess && n) e = hipMalloc(&d_t, n * sizeof(Tuple));
     if (e == hipSuccess && n && h_weights) e = hipMalloc(&d_wt, n * sizeof(uint32_t));
+    if (e == hipSuccess && n && h_extra) e = hipMalloc(&d_x, n * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMalloc(&d_c, count_bytes + scratch_bytes);
     if (e == hipSuccess && window_bytes)
         e = hipMemcpyAsync(d_w, windows.data(), window_bytes, hipMemcpyHostToDevice, s);
@@ -213,11 +234,14 @@ int key_host_run(const char* who, rss_ctx* ctx, const std::vector<uint32_t>& win
         e = hipMemcpyAsync(d_t, h_tuples, n * sizeof(Tuple), hipMemcpyHostToDevice, s);
     if (e == hipSuccess && n && h_weights)
         e = hipMemcpyAsync(d_wt, h_weights, n * sizeof(uint32_t), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && n && h_extra)
+        e = hipMemcpyAsync(d_x, h_extra, n * sizeof(uint32_t), hipMemcpyHostToDevice, s);
     if (e != hipSuccess) {
         cleanup();
         return rss_set_error(e == hipErrorOutOfMemory ? RSS_ENOMEM : RSS_EIO, "%s: %s", who,
                              hipGetErrorString(e));
     }
+    if (d_extra) *d_extra = d_x;
     int rc = launch(d_w, d_t, d_wt, d_c, s);
     if (rc == RSS_OK) {
         e = hipMemcpyAsync(h_counts, d_c, count_bytes, hipMemcpyDeviceToHost, s);
@@ -428,6 +452,18 @@ int rss_key_neighbourhood_weighted_device(const rss_key* key, const rss_tuple4* 
     if (rc) return rc;
     return rss::launch_neighbourhood_weighted(key, d_tuples, d_weights, n, htable, nqueues, d_loads,
                                               static_cast<hipStream_t>(stream));
+}
+
+int rss_key_search_timeline_device(const uint32_t* d_windows, size_t nkeys,
+                                   const rss_tuple4* d_tuples, const uint32_t* d_weights,
+                                   const uint32_t* d_slots, size_t n, uint32_t nslots,
+                                   uint32_t htable, uint32_t nqueues, uint64_t* d_loads,
+                                   void* stream) {
+    int rc = check_timeline("rss_key_search_timeline_device", "windows", d_windows, nkeys, d_tuples,
+                            d_slots, n, nslots, htable, nqueues, d_loads);
+    if (rc) return rc;
+    return rss::launch_search_timeline(d_windows, nkeys, d_tuples, d_weights, d_slots, n, nslots,
+                                       htable, nqueues, d_loads, static_cast<hipStream_t>(stream));
 }
 
 int rss_key_byte_neighbourhood_device(const rss_key* key, uint32_t first_byte, uint32_t nbytes,
@@ -1018,6 +1054,35 @@ int rss_key_search_weighted_host(rss_ctx* ctx, const rss_key* keys, size_t nkeys
                             return rss::launch_search_weighted(d_w, nkeys, d_t, d_wt, n, htable,
                                                                nqueues, d_c, s);
                         }, h_weights);
+}
+
+int rss_key_search_timeline_host(rss_ctx* ctx, const rss_key* keys, size_t nkeys,
+                                 const rss_tuple4* h_tuples, const uint32_t* h_weights,
+                                 const uint32_t* h_slots, size_t n, uint32_t nslots,
+                                 uint32_t htable, uint32_t nqueues, uint64_t* h_loads) {
+    const char* who = "rss_key_search_timeline_host";
+    int rc = check_timeline(who, "keys", keys, nkeys, h_tuples, h_slots, n, nslots, htable, nqueues,
+                            h_loads);
+    if (rc) return rc;
+    if (!ctx) return rss_set_error(RSS_EINVAL, "%s: context is NULL", who);
+    std::vector<uint32_t> windows(nkeys * RSS_INPUT_BITS);
+    for (size_t k = 0; k < nkeys; ++k) {
+        if (keys[k].len < RSS_KEY_MIN_BYTES)
+            return rss_set_error(RSS_EINVAL, "%s: key %zu not prepared", who, k);
+        memcpy(&windows[k * RSS_INPUT_BITS], keys[k].window, sizeof keys[k].window);
+    }
+    const size_t load_bytes = nkeys * nslots * nqueues * sizeof(uint64_t);
+    if (n == 0) {
+        memset(h_loads, 0, load_bytes);
+        return RSS_OK;
+    }
+    uint32_t* d_slots = nullptr;
+    return key_host_run(who, ctx, windows, h_tuples, n, load_bytes, h_loads,
+                        [&](uint32_t* d_w, rss_tuple4* d_t, uint32_t* d_wt, uint64_t* d_c,
+                            hipStream_t s) {
+                            return rss::launch_search_timeline(d_w, nkeys, d_t, d_wt, d_slots, n,
+                                                               nslots, htable, nqueues, d_c, s);
+                        }, h_weights, 0, h_slots, &d_slots);
 }
 
 int rss_key_neighbourhood_weighted_host(rss_ctx* ctx, const rss_key* key,

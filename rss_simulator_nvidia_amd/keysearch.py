@@ -31,6 +31,13 @@ GPU (``rss_flow_aggregate_device``: a hash set of packet indices, first-seen ord
 flow's load is the sum of its rows' ``--weight-column``, or its row count without one.
 ``--pcap`` de-duplicates its packets the same way.
 
+``--time-column NAME --window WIDTH`` take a CSV with one row per packet and a numeric time:
+the ranking is unchanged (rows are packets, so it is by packet load, or by ``--weight-column``),
+and each listed key then gets a line ``peak P at window S of W`` -- its hottest queue in any
+window, relative to the busiest window's ideal share (:func:`timeline`, :func:`peak`; one
+``rss_key_search_timeline_device`` launch; IPv4).  A key that is level over the whole capture
+can still put two heavy flows on one queue in the same window; the peak shows it.
+
 ``--symmetric`` ranks the 65536 symmetric keys instead -- a 16-bit pattern repeated over the
 key (DPDK's ``6d:5a:6d:5a:...``), which sends both directions of a connection to one queue.
 Their hash depends only on the XOR of a tuple's 16-bit half-words, so the flows are folded
@@ -114,6 +121,64 @@ def evaluate(keys, tuples, htable, nqueues, ctx=None, ipv6=False, weights=None):
     if weights is None:
         return ctx.key_search(prepared, tuples, htable, nqueues)
     return ctx.key_search(prepared, tuples, htable, nqueues, weights=weights)
+
+
+def timeline(keys, tuples, slots, htable, nqueues, nslots=None, weights=None, ctx=None,
+             ipv6=False):
+    """uint64 loads ``[len(keys), nslots, min(H, Q)]`` of the packets ``tuples`` under every
+    key, per time window (GPU, one launch: ``rss_key_search_timeline_device``): packet i falls
+    into window ``slots[i]`` (an integer in [0, 2^32)) and adds ``weights[i]`` (one integer in
+    [0, 2^32) per packet; 1 without ``weights``) to its queue there.  ``nslots`` defaults to
+    ``slots.max() + 1``; packets in windows ``>= nslots`` are left out.  Any order of the slots
+    is exact; time order is what makes it fast.  IPv4 only, like the weighted entries."""
+    if ipv6:
+        raise NotImplementedError("timeline with ipv6=True: the weighted key-search kernels "
+                                  "serve IPv4 tuples only")
+    s = _native.tuple_slots(slots, len(tuples))
+    if nslots is None:
+        nslots = int(s.max()) + 1 if len(s) else 1
+    if int(nslots) < 1 or int(nslots) > 0xFFFFFFFF:
+        raise ValueError("nslots must lie in [1, 2^32), got %r" % (nslots,))
+    ctx = ctx or _native.default_context()
+    return ctx.key_search_timeline([_native.prepare_key(k) for k in keys], tuples, s, int(nslots),
+                                   htable, nqueues, weights=weights)
+
+
+def peak(loads, htable, nqueues):
+    """How far the hottest (window, queue) of ``loads`` (``[keys, windows, min(H, Q)]`` from
+    :func:`timeline`, or one key's ``[windows, min(H, Q)]``) stands above the busiest window's
+    ideal share: ``peak`` = max over (s, q) of ``loads[s, q] / slot_share[q]``, divided by the
+    max over s of ``loads[s].sum()`` -- 1.0 means the busiest window was perfectly level and no
+    other window's queue exceeded it; 0.0 for no load at all.  Returns a dict of per-key arrays:
+    ``peak`` and ``window``, the window where it occurs."""
+    loads = np.asarray(loads, dtype=np.float64)
+    if loads.ndim == 2:
+        loads = loads[None]
+    rel = loads / slot_share(htable, nqueues, loads.shape[2])[None, None, :]
+    busiest = loads.sum(axis=2).max(axis=1)
+    hot = rel.max(axis=2)  # [keys, windows]
+    return {"peak": np.where(busiest > 0, hot.max(axis=1) / np.where(busiest > 0, busiest, 1), 0.0),
+            "window": hot.argmax(axis=1)}
+
+
+def window_slots(times, width):
+    """``(slots, nslots)`` of per-packet ``times``: ``slots[i] = floor((times[i] - t_min) /
+    width)`` as uint32, ``width`` in the units of ``times``.  ``ValueError`` unless the times are
+    finite numbers, ``width > 0`` and the windows number fewer than 2^32."""
+    t = np.asarray(times)
+    if t.ndim != 1 or t.dtype.kind not in "iuf":
+        raise ValueError("times must be one number per packet, not %s" % t.dtype)
+    if not width > 0:
+        raise ValueError("the window width must be > 0, got %r" % (width,))
+    t = t.astype(np.float64)
+    if not np.isfinite(t).all():
+        raise ValueError("times must be finite numbers")
+    if len(t) == 0:
+        return np.zeros(0, dtype=np.uint32), 1
+    slots = np.floor((t - t.min()) / float(width))
+    if slots.max() >= 2.0**32:
+        raise ValueError("%g windows of width %r: more than 2^32" % (slots.max() + 1, width))
+    return slots.astype(np.uint32), int(slots.max()) + 1
 
 
 def search(tuples, htable, nqueues, n_keys=1024, seed=0, top=10, extra_keys=(), ipv6=False,
@@ -392,6 +457,23 @@ def load_weighted_csv(ips_file, column):
     return pack_frame(df), _native.tuple_weights(df[column].to_numpy(), len(df))
 
 
+def load_timed_csv(ips_file, time_column, width, weight_column=None):
+    """``(tuples, weights, slots, nslots)`` of a CSV with one row per packet: the packed
+    tuples, the ``weight_column`` (or None), and each packet's window from the numeric
+    ``time_column`` (:func:`window_slots`).  ``ValueError`` for a missing column or bad values."""
+    df = pd.read_csv(ips_file)
+    for column in (time_column, weight_column):
+        if column is not None and column not in df.columns:
+            raise ValueError("%s has no column %r" % (ips_file, column))
+    if df[time_column].dtype.kind not in "iuf":
+        raise ValueError("column %r of %s is not numeric" % (time_column, ips_file))
+    slots, nslots = window_slots(df[time_column].to_numpy(), width)
+    weights = None
+    if weight_column is not None:
+        weights = _native.tuple_weights(df[weight_column].to_numpy(), len(df))
+    return pack_frame(df), weights, slots, nslots
+
+
 def load_weighted_csv6(ips_file, column):
     """:func:`load_weighted_csv` for a CSV of IPv6 flows (``TUPLE6_DTYPE`` tuples)."""
     df = pd.read_csv(ips_file)
@@ -453,7 +535,21 @@ def main(argv=None):
                    help="the CSV holds one row per packet: fold the rows to flows (on the GPU) "
                         "and rank by load, the sum of --weight-column per flow or the rows per "
                         "flow without it")
+    p.add_argument("--time-column", metavar="NAME",
+                   help="the CSV holds one row per packet and NAME is its numeric time: after "
+                        "the ranking, print each listed key's peak -- its hottest queue in any "
+                        "window of --window, relative to the busiest window's ideal share")
+    p.add_argument("--window", metavar="WIDTH", type=float,
+                   help="width of a time window, in the units of --time-column")
     args = p.parse_args(argv)
+    if (args.time_column is None) != (args.window is None):
+        p.error("--time-column and --window go together: the column holds each packet's time, "
+                "the width cuts it into windows")
+    if args.time_column and (args.pcap or args.ipv6 or args.aggregate):
+        p.error("--time-column cannot be combined with --pcap, --ipv6 or --aggregate: the "
+                "timeline takes the rows of an IPv4 CSV as packets")
+    if args.window is not None and not args.window > 0:
+        p.error("--window must be > 0, got %r" % args.window)
     if args.aggregate and args.pcap:
         p.error("--aggregate folds the rows of a CSV: not allowed with --pcap, whose packets "
                 "are always folded to flows")
@@ -474,10 +570,17 @@ def main(argv=None):
                 "search serves IPv4 flows only")
     if args.pcap and args.weight_column:
         p.error("--weight-column names a CSV column: not allowed with --pcap")
+    slots = None
     if args.pcap:
         from rss_simulator_nvidia_amd.pcap import read_flows
         tuples, _, _, weights = read_flows(args.pcap, ipv6=args.ipv6, packet_counts=True,
                                            on_device=True)
+    elif args.time_column:
+        try:
+            tuples, weights, slots, nslots = load_timed_csv(args.ips_file, args.time_column,
+                                                            args.window, args.weight_column)
+        except ValueError as err:
+            p.error("--time-column %s: %s" % (args.time_column, err))
     elif args.weight_column:
         try:
             tuples, weights = (load_weighted_csv6 if args.ipv6 else load_weighted_csv)(
@@ -523,6 +626,15 @@ def main(argv=None):
             print("%s  max_load %.4f chi2 %.2f queues used %d"
                   % (key_text(r["key"]), r["max_load"], r["chi2"], r["used"]))
         ranked = refined + ranked  # --out takes the best refined key
+    if slots is not None:  # one timeline launch over every key listed above
+        listed = []
+        for key in [list(k) for k in extra] + [list(r["key"]) for r in ranked]:
+            if key not in listed:
+                listed.append(key)
+        pk = peak(timeline(listed, tuples, slots, args.htable_size, args.num_queues, nslots,
+                           weights), args.htable_size, args.num_queues)
+        for key, value, window in zip(listed, pk["peak"], pk["window"]):
+            print("%s  peak %.4f at window %d of %d" % (key_text(key), value, window, nslots))
     if args.out:
         with open(args.out, "w") as f:
             f.write(key_text(ranked[0]["key"]))
