@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define RSS_ABI_VERSION 1
+#define RSS_ABI_VERSION 2
 
 /* status codes (negative errno values) */
 #define RSS_OK 0
@@ -302,6 +302,47 @@ int rss_key_search_timeline_device(const uint32_t* d_windows, size_t nkeys,
                                    const uint32_t* d_slots, size_t n, uint32_t nslots,
                                    uint32_t htable, uint32_t nqueues, uint64_t* d_loads,
                                    void* stream);
+
+/*
+ * Key search by backlog: the deepest each queue's ring gets under each key -- what a NIC ring
+ * and its core see, whatever window a timeline would be cut into.  One row per packet, in time
+ * order: d_tuples[i], its weight d_weights[i] (n uint32, or NULL for 1 per packet) and its tick
+ * d_ticks[i] (n uint32, non-decreasing).  Every queue drains `drain` weight units per tick
+ * (0 <= drain < 2^31).  Under key k packet i joins queue q = hash_k % htable % nqueues, whose
+ * backlog just after it is
+ *     B = max(B_prev - drain * (d_ticks[i] - tick_prev), 0) + weight
+ * (B_prev, tick_prev: the queue's previous packet; B = 0 before its first).  d_peaks: nkeys x
+ * nqueues uint64, overwritten: d_peaks[k][q] is the largest B queue q reaches, 0 if it gets no
+ * packet; columns [min(htable, nqueues), nqueues) are zero.  Exact in 64-bit integers for any
+ * u32 weights and ticks, any htable, n < 2^31 and any 4-byte aligned pointers; packets of equal
+ * ticks may come in any order; with drain == 0 the peak is the queue's load
+ * (rss_key_search_weighted_device).  Ticks that decrease are a broken precondition: the peaks
+ * are then unspecified, but ticks are only ever used in arithmetic, never as an index.
+ * Two kernels and no waiting between workgroups: the stream is cut into at most min(ceil(n /
+ * 256), 8192) segments of consecutive packets, each reduced to four 64-bit values per (key,
+ * queue) by one lane stepping through the segment's staged queue ids, and a second kernel chains
+ * the segments in order (rss_backlog.hip).  With q = min(htable, nqueues):
+ *   power-of-two htable <= 256, nkeys > 4, q <= 128      8 keys per workgroup
+ *   power-of-two htable <= 65536, nkeys > 1, q <= 255    4 keys
+ *   anything else                                        1 key; its states in LDS past q = 1024
+ *   q > 4096 is refused.
+ * d_workspace: workspace_bytes >= rss_key_search_backlog_workspace_bytes(nkeys, n, htable,
+ * nqueues) bytes of 8-byte aligned device memory, any contents, used by one call at a time; the
+ * size is a function of those four arguments alone.  The call is stream-ordered, allocates
+ * nothing and waits for nothing, so it can be captured into a graph; n == 0 only clears.
+ * RSS_EINVAL, before any device work, with rss_last_error naming the entry and the cause:
+ * windows, peaks or ticks NULL; nkeys == 0; n > 0 with tuples NULL; htable or nqueues 0; drain
+ * >= 2^31; n >= 2^31; min(htable, nqueues) > 4096; a workspace that is NULL, misaligned or too
+ * small (the message gives the bytes needed); for the size function a NULL out.  IPv6 tuples are
+ * out of scope.
+ */
+int rss_key_search_backlog_workspace_bytes(size_t nkeys, size_t n, uint32_t htable,
+                                           uint32_t nqueues, size_t* out);
+int rss_key_search_backlog_device(const uint32_t* d_windows, size_t nkeys,
+                                  const rss_tuple4* d_tuples, const uint32_t* d_weights,
+                                  const uint32_t* d_ticks, size_t n, uint32_t drain,
+                                  uint32_t htable, uint32_t nqueues, uint64_t* d_peaks,
+                                  void* d_workspace, size_t workspace_bytes, void* stream);
 
 /*
  * Symmetric RSS: rank the keys that hash both directions of a connection to one queue.  A key
@@ -683,6 +724,16 @@ int rss_key_search_timeline_host(rss_ctx* ctx, const rss_key* keys, size_t nkeys
                                  const rss_tuple4* h_tuples, const uint32_t* h_weights,
                                  const uint32_t* h_slots, size_t n, uint32_t nslots,
                                  uint32_t htable, uint32_t nqueues, uint64_t* h_loads);
+
+/* rss_key_search_backlog_device on host buffers (keys: nkeys prepared keys; h_weights: n uint32
+ * or NULL; h_ticks: n uint32, non-decreasing; h_peaks: nkeys x nqueues uint64), as
+ * rss_key_search_timeline_host: takes the context's lock, uploads, launches on a workspace of
+ * its own, copies the peaks back.  Synchronous.  The same validation (and a NULL ctx, or a key
+ * that was not prepared) is refused first; n == 0 zeroes h_peaks on the host. */
+int rss_key_search_backlog_host(rss_ctx* ctx, const rss_key* keys, size_t nkeys,
+                                const rss_tuple4* h_tuples, const uint32_t* h_weights,
+                                const uint32_t* h_ticks, size_t n, uint32_t drain, uint32_t htable,
+                                uint32_t nqueues, uint64_t* h_peaks);
 
 /* rss_symmetric_fold_device + rss_symmetric_search_device on host buffers (described with
  * them): h_tuples n x `words` uint32, h_weights n uint32 or NULL, h_loads npatterns x nqueues

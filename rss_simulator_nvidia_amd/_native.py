@@ -19,7 +19,7 @@ LIB_NAME = "librss_toeplitz.so"
 LIB_PATH = os.environ.get(
     "RSS_TOEPLITZ_LIB", os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME))
 
-ABI_VERSION = 1
+ABI_VERSION = 2
 FLAG_ACCUMULATE = 1
 FLAG_QUEUE_U16 = 2
 FLAG_QUEUE_U8 = 4
@@ -51,6 +51,8 @@ EXPORTED_SYMBOLS = (
     "rss_key_byte_neighbourhood_weighted_device", "rss_key_byte_neighbourhood_host",
     "rss_key_byte_neighbourhood6_host", "rss_key_byte_neighbourhood_weighted_host",
     "rss_key_search_timeline_device", "rss_key_search_timeline_host",
+    "rss_key_search_backlog_workspace_bytes", "rss_key_search_backlog_device",
+    "rss_key_search_backlog_host",
 )
 SYMMETRIC_PATTERNS = 65536  # RSS_SYMMETRIC_PATTERNS: 16-bit key patterns = fold values
 KEY_NEIGHBOURS = 128  # RSS_KEY_NEIGHBOURS: the key bits an IPv4 hash reads
@@ -131,6 +133,12 @@ def _bind(lib):
                                            ctypes.c_int),
         "rss_key_search_timeline_host": ([vp, vp, sz, vp, vp, vp, sz, u32, u32, u32, vp],
                                          ctypes.c_int),
+        "rss_key_search_backlog_workspace_bytes": ([sz, sz, u32, u32, ctypes.POINTER(sz)],
+                                                   ctypes.c_int),
+        "rss_key_search_backlog_device": ([vp, sz, vp, vp, vp, sz, u32, u32, u32, vp, vp, sz, vp],
+                                          ctypes.c_int),
+        "rss_key_search_backlog_host": ([vp, vp, sz, vp, vp, vp, sz, u32, u32, u32, vp],
+                                        ctypes.c_int),
         "rss_key_byte_neighbourhood_device": ([key_p, u32, u32, vp, sz, u32, u32, vp, vp],
                                               ctypes.c_int),
         "rss_key_byte_neighbourhood_host": ([vp, key_p, u32, u32, vp, sz, u32, u32, vp],
@@ -591,6 +599,25 @@ class HostContext:
             "rss_key_search_timeline_host")
         return out
 
+    def key_search_backlog(self, keys, tuples, ticks, drain, htable, nqueues, weights=None):
+        """Peak backlog per queue (uint64[len(keys), min(htable, nqueues)]) of the time-ordered
+        packets ``tuples`` under each prepared key (``rss_key_search_backlog_host``): packet i
+        arrives at tick ``ticks[i]`` (non-decreasing) with ``weights[i]`` units (1 without
+        ``weights``), and every queue drains ``drain`` units per tick."""
+        htable, nqueues = queue_modulus(htable, nqueues)
+        arr = np.ascontiguousarray(tuples)
+        if arr.dtype != TUPLE_DTYPE:
+            arr = np.ascontiguousarray(arr, dtype=np.uint32).reshape(-1, 3)
+        t = tuple_ticks(ticks, len(arr))
+        w = None if weights is None else tuple_weights(weights, len(arr))
+        drain = backlog_drain(drain)
+        karr = (RssKey * len(keys))(*keys)
+        out = np.zeros((len(keys), nqueues), dtype=np.uint64)
+        _check(self._lib.rss_key_search_backlog_host(
+            self._ctx, karr, len(keys), arr.ctypes.data, ptr(w), t.ctypes.data, len(arr), drain,
+            htable, nqueues, out.ctypes.data), "rss_key_search_backlog_host")
+        return out
+
     def key_neighbourhood(self, key, tuples, htable, nqueues, weights=None):
         """Per-queue counts (uint64[128, min(htable, nqueues)]) of ``tuples`` under each
         single-bit flip of the prepared ``key`` (``rss_key_neighbourhood_host``): row j has
@@ -752,6 +779,30 @@ def tuple_slots(slots, n):
     if len(s) and (s.min() < 0 or s.max() > 0xFFFFFFFF):
         raise ValueError("slots must lie in [0, 2^32)")
     return np.ascontiguousarray(s, dtype=np.uint32)
+
+
+def tuple_ticks(ticks, n):
+    """``ticks`` as contiguous uint32[n] for the backlog entry: one arrival tick in [0, 2^32)
+    per packet, non-decreasing; anything else is a ``ValueError``."""
+    t = np.asarray(ticks)
+    if t.ndim != 1 or len(t) != n:
+        raise ValueError("ticks: expected one tick per packet (%d), got shape %s" % (n, t.shape))
+    if t.dtype.kind not in "iu":
+        raise ValueError("ticks must be integers, not %s" % t.dtype)
+    if len(t) and (t.min() < 0 or t.max() > 0xFFFFFFFF):
+        raise ValueError("ticks must lie in [0, 2^32)")
+    t = np.ascontiguousarray(t, dtype=np.uint32)
+    if len(t) > 1 and (t[1:] < t[:-1]).any():
+        raise ValueError("ticks must be non-decreasing: the packets are taken in time order")
+    return t
+
+
+def backlog_drain(drain):
+    """``drain`` as the backlog entries' integer in [0, 2^31), else a ``ValueError``."""
+    if isinstance(drain, bool) or not isinstance(drain, (int, np.integer)) \
+            or not 0 <= int(drain) < 2**31:
+        raise ValueError("drain must be an integer in [0, 2^31), got %r" % (drain,))
+    return int(drain)
 
 
 def _tuples6(tuples):
@@ -956,6 +1007,29 @@ def key_search_timeline_device(windows_ptr, nkeys, tuples_ptr, weights_ptr, slot
                                                  slots_ptr, n, nslots, htable, nqueues, loads_ptr,
                                                  stream),
            "rss_key_search_timeline_device")
+
+
+def key_search_backlog_workspace_bytes(nkeys, n, htable, nqueues):
+    """Bytes of the workspace ``rss_key_search_backlog_device`` needs: a bound that depends on
+    these four arguments alone."""
+    out = ctypes.c_size_t()
+    _check(load().rss_key_search_backlog_workspace_bytes(nkeys, n, htable, nqueues,
+                                                         ctypes.byref(out)),
+           "rss_key_search_backlog_workspace_bytes")
+    return out.value
+
+
+def key_search_backlog_device(windows_ptr, nkeys, tuples_ptr, weights_ptr, ticks_ptr, n, drain,
+                              htable, nqueues, peaks_ptr, workspace_ptr, workspace_bytes,
+                              stream=None):
+    """Stream-ordered ``rss_key_search_backlog_device`` on raw device pointers (ints):
+    ``weights_ptr`` (n uint32, or None for 1 per packet) and ``ticks_ptr`` (n uint32,
+    non-decreasing) beside the tuples, ``peaks_ptr`` = uint64[nkeys, nqueues] (overwritten),
+    ``workspace_ptr`` at least :func:`key_search_backlog_workspace_bytes` bytes."""
+    _check(load().rss_key_search_backlog_device(windows_ptr, nkeys, tuples_ptr, weights_ptr,
+                                                ticks_ptr, n, drain, htable, nqueues, peaks_ptr,
+                                                workspace_ptr, workspace_bytes, stream),
+           "rss_key_search_backlog_device")
 
 
 def key_neighbourhood_weighted_device(key, tuples_ptr, weights_ptr, n, htable, nqueues, loads_ptr,

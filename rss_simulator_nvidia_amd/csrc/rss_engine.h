@@ -1,6 +1,7 @@
 // rss_engine.h -- the engine's launchers (rss_toeplitz.hip, rss_keysearch.hip,
 // rss_keysearch6.hip, rss_neighbourhood.hip, rss_byte_neighbourhood.hip,
-// rss_keysearch_weighted.hip, rss_timeline.hip, rss_symmetric.hip, rss_flow_aggregate.hip) as the C ABI (rss_host.hip) calls
+// rss_keysearch_weighted.hip, rss_timeline.hip, rss_backlog.hip, rss_symmetric.hip,
+// rss_flow_aggregate.hip) as the C ABI (rss_host.hip) calls
 // them, and the HIP error macro both use.  Internal, not ABI.
 #pragma once
 
@@ -66,6 +67,18 @@ RSS_HIDDEN int launch_search_timeline(const uint32_t* d_windows, size_t nkeys,
                                       const uint32_t* d_slots, size_t n, uint32_t nslots,
                                       uint32_t htable, uint32_t nqueues, uint64_t* d_loads,
                                       hipStream_t stream);
+// rss_key_search_backlog_workspace_bytes / rss_key_search_backlog_device (rss_backlog.hip;
+// arguments validated by the caller: min(htable, nqueues) <= backlog_max_queues(), the workspace
+// 8-byte aligned and large enough; d_weights may be NULL).  backlog_workspace_bytes: false when
+// the size overflows size_t.
+RSS_HIDDEN uint32_t backlog_max_queues();
+RSS_HIDDEN bool backlog_workspace_bytes(size_t nkeys, size_t n, uint32_t htable, uint32_t nqueues,
+                                        size_t* out);
+RSS_HIDDEN int launch_search_backlog(const uint32_t* d_windows, size_t nkeys,
+                                     const rss_tuple4* d_tuples, const uint32_t* d_weights,
+                                     const uint32_t* d_ticks, size_t n, uint32_t drain,
+                                     uint32_t htable, uint32_t nqueues, uint64_t* d_peaks,
+                                     void* d_workspace, hipStream_t stream);
 // rss_key_byte_neighbourhood_device / _weighted_device (d_weights non-NULL) / 6_device
 // (rss_byte_neighbourhood.hip; arguments validated by the caller)
 RSS_HIDDEN int launch_byte_neighbourhood(const rss_key* key, uint32_t first_byte, uint32_t nbytes,

@@ -156,6 +156,29 @@ int check_timeline(const char* who, const char* what, const void* windows_or_key
     return RSS_OK;
 }
 
+// rss_key_search_backlog_device / _host
+int check_backlog(const char* who, const char* what, const void* windows_or_keys, size_t nkeys,
+                  const void* tuples, const uint32_t* ticks, size_t n, uint32_t drain,
+                  uint32_t htable, uint32_t nqueues, const uint64_t* peaks) {
+    if (!windows_or_keys || !peaks)
+        return rss_set_error(RSS_EINVAL, "%s: %s or peaks is NULL", who, what);
+    if (!ticks) return rss_set_error(RSS_EINVAL, "%s: ticks is NULL", who);
+    if (nkeys == 0) return rss_set_error(RSS_EINVAL, "%s: no keys", who);
+    if (n && !tuples) return rss_set_error(RSS_EINVAL, "%s: tuples is NULL", who);
+    if (htable < 1 || nqueues < 1)
+        return rss_set_error(RSS_EINVAL, "%s: htable (%u) and nqueues (%u) must be >= 1", who,
+                             htable, nqueues);
+    if (drain >= 0x80000000u)
+        return rss_set_error(RSS_EINVAL, "%s: drain %u must be below 2^31", who, drain);
+    if (n >= ((size_t)1 << 31))
+        return rss_set_error(RSS_EINVAL, "%s: %zu packets: n must be below 2^31", who, n);
+    if (std::min(htable, nqueues) > rss::backlog_max_queues())
+        return rss_set_error(RSS_EINVAL, "%s: min(htable, nqueues) = %u exceeds the %u queues served",
+                             who, std::min(htable, nqueues), rss::backlog_max_queues());
+    if (nkeys > 0xFFFFFFFFu) return rss_set_error(RSS_EINVAL, "%s: %zu keys exceed 2^32", who, nkeys);
+    return RSS_OK;
+}
+
 // rss_symmetric_fold_device / rss_symmetric_search_host: the flow set
 int check_symmetric_fold(const char* who, const void* tuples, uint32_t words, uint32_t fields,
                          size_t n) {
@@ -198,7 +221,8 @@ int check_flow_aggregate(const char* who, const void* tuples, uint32_t words, si
 // context's lock upload `windows` (search only; empty otherwise), the tuples and their weights
 // (weighted only; NULL otherwise), `launch(d_windows, d_tuples, d_weights, d_counts, stream)`,
 // copy count_bytes of counts back.  `scratch_bytes` more device bytes follow the counts (the
-// symmetric search's folds).  `h_extra` (the timeline's slots; NULL otherwise): n more uint32
+// symmetric search's folds, the backlog's workspace).  `h_extra` (the timeline's slots, the
+// backlog's ticks; NULL otherwise): n more uint32
 // uploaded, their device copy in *d_extra before `launch` runs.  Synchronous.
 template <typename Tuple, typename Launch>
 int key_host_run(const char* who, rss_ctx* ctx, const std::vector<uint32_t>& windows,
@@ -534,6 +558,42 @@ int rss_symmetric_search_device(const uint64_t* d_folds, uint32_t first_pattern,
     if (rc) return rc;
     return rss::launch_symmetric_search(d_folds, first_pattern, npatterns, htable, nqueues, d_loads,
                                         static_cast<hipStream_t>(stream));
+}
+
+int rss_key_search_backlog_workspace_bytes(size_t nkeys, size_t n, uint32_t htable,
+                                           uint32_t nqueues, size_t* out) {
+    const char* who = "rss_key_search_backlog_workspace_bytes";
+    if (!out) return rss_set_error(RSS_EINVAL, "%s: NULL argument", who);
+    if (nkeys == 0) return rss_set_error(RSS_EINVAL, "%s: no keys", who);
+    if (htable < 1 || nqueues < 1)
+        return rss_set_error(RSS_EINVAL, "%s: htable (%u) and nqueues (%u) must be >= 1", who,
+                             htable, nqueues);
+    if (!rss::backlog_workspace_bytes(nkeys, n, htable, nqueues, out))
+        return rss_set_error(RSS_EINVAL, "%s: the size exceeds size_t", who);
+    return RSS_OK;
+}
+
+int rss_key_search_backlog_device(const uint32_t* d_windows, size_t nkeys,
+                                  const rss_tuple4* d_tuples, const uint32_t* d_weights,
+                                  const uint32_t* d_ticks, size_t n, uint32_t drain,
+                                  uint32_t htable, uint32_t nqueues, uint64_t* d_peaks,
+                                  void* d_workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "rss_key_search_backlog_device";
+    int rc = check_backlog(who, "windows", d_windows, nkeys, d_tuples, d_ticks, n, drain, htable,
+                           nqueues, d_peaks);
+    if (rc) return rc;
+    size_t need = 0;
+    if (!rss::backlog_workspace_bytes(nkeys, n, htable, nqueues, &need))
+        return rss_set_error(RSS_EINVAL, "%s: the workspace size exceeds size_t", who);
+    if (!d_workspace || ((uintptr_t)d_workspace & 7u))
+        return rss_set_error(RSS_EINVAL, "%s: workspace NULL or not 8-byte aligned (%zu bytes needed)",
+                             who, need);
+    if (workspace_bytes < need)
+        return rss_set_error(RSS_EINVAL, "%s: workspace of %zu bytes, %zu keys and %zu packets need %zu",
+                             who, workspace_bytes, nkeys, n, need);
+    return rss::launch_search_backlog(d_windows, nkeys, d_tuples, d_weights, d_ticks, n, drain,
+                                      htable, nqueues, d_peaks, d_workspace,
+                                      static_cast<hipStream_t>(stream));
 }
 
 int rss_flow_aggregate_workspace_bytes(size_t n, uint32_t words, size_t* out) {
@@ -1083,6 +1143,40 @@ int rss_key_search_timeline_host(rss_ctx* ctx, const rss_key* keys, size_t nkeys
                             return rss::launch_search_timeline(d_w, nkeys, d_t, d_wt, d_slots, n,
                                                                nslots, htable, nqueues, d_c, s);
                         }, h_weights, 0, h_slots, &d_slots);
+}
+
+int rss_key_search_backlog_host(rss_ctx* ctx, const rss_key* keys, size_t nkeys,
+                                const rss_tuple4* h_tuples, const uint32_t* h_weights,
+                                const uint32_t* h_ticks, size_t n, uint32_t drain, uint32_t htable,
+                                uint32_t nqueues, uint64_t* h_peaks) {
+    const char* who = "rss_key_search_backlog_host";
+    int rc = check_backlog(who, "keys", keys, nkeys, h_tuples, h_ticks, n, drain, htable, nqueues,
+                           h_peaks);
+    if (rc) return rc;
+    if (!ctx) return rss_set_error(RSS_EINVAL, "%s: context is NULL", who);
+    size_t ws_bytes = 0;
+    if (!rss::backlog_workspace_bytes(nkeys, n, htable, nqueues, &ws_bytes))
+        return rss_set_error(RSS_EINVAL, "%s: the workspace size exceeds size_t", who);
+    std::vector<uint32_t> windows(nkeys * RSS_INPUT_BITS);
+    for (size_t k = 0; k < nkeys; ++k) {
+        if (keys[k].len < RSS_KEY_MIN_BYTES)
+            return rss_set_error(RSS_EINVAL, "%s: key %zu not prepared", who, k);
+        memcpy(&windows[k * RSS_INPUT_BITS], keys[k].window, sizeof keys[k].window);
+    }
+    const size_t peak_bytes = nkeys * nqueues * sizeof(uint64_t);
+    if (n == 0) {
+        memset(h_peaks, 0, peak_bytes);
+        return RSS_OK;
+    }
+    // the workspace lives behind the peaks in one allocation (8-byte aligned there)
+    uint32_t* d_ticks = nullptr;
+    return key_host_run(who, ctx, windows, h_tuples, n, peak_bytes, h_peaks,
+                        [&](uint32_t* d_w, rss_tuple4* d_t, uint32_t* d_wt, uint64_t* d_c,
+                            hipStream_t s) {
+                            return rss::launch_search_backlog(d_w, nkeys, d_t, d_wt, d_ticks, n,
+                                                              drain, htable, nqueues, d_c,
+                                                              d_c + nkeys * nqueues, s);
+                        }, h_weights, ws_bytes, h_ticks, &d_ticks);
 }
 
 int rss_key_neighbourhood_weighted_host(rss_ctx* ctx, const rss_key* key,

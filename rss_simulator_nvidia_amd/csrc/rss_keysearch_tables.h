@@ -3,7 +3,8 @@
 // pair tables; described in rss_keysearch.hip), the neighbourhood's per-tuple flip span
 // (rss_neighbourhood.hip) with its IPv6 tables and span, the u64 load rows and the launch-grid
 // rules.  Used by rss_keysearch.hip, rss_neighbourhood.hip, rss_byte_neighbourhood.hip,
-// rss_keysearch_weighted.hip, rss_timeline.hip and rss_symmetric.hip; anonymous namespace, as
+// rss_keysearch_weighted.hip, rss_timeline.hip, rss_backlog.hip and rss_symmetric.hip; anonymous
+// namespace, as
 // rss_kernel_common.h.
 #pragma once
 

@@ -38,6 +38,13 @@ window, relative to the busiest window's ideal share (:func:`timeline`, :func:`p
 ``rss_key_search_timeline_device`` launch; IPv4).  A key that is level over the whole capture
 can still put two heavy flows on one queue in the same window; the peak shows it.
 
+``--drain UNITS --tick WIDTH`` (with ``--time-column``) add what a NIC ring sees, whatever the
+window: every queue drains ``UNITS`` of load per tick of ``WIDTH`` time units, a packet arriving
+at a queue raises its backlog by its weight, and each listed key gets a line ``backlog B at queue
+Q`` -- the deepest any queue's backlog gets over the capture (:func:`backlog`; one
+``rss_key_search_backlog_device`` call, exact in 64-bit integers; IPv4).  A burst across a
+window edge or a microburst inside a wide window shows here as it is.
+
 ``--symmetric`` ranks the 65536 symmetric keys instead -- a 16-bit pattern repeated over the
 key (DPDK's ``6d:5a:6d:5a:...``), which sends both directions of a connection to one queue.
 Their hash depends only on the XOR of a tuple's 16-bit half-words, so the flows are folded
@@ -142,6 +149,21 @@ def timeline(keys, tuples, slots, htable, nqueues, nslots=None, weights=None, ct
     ctx = ctx or _native.default_context()
     return ctx.key_search_timeline([_native.prepare_key(k) for k in keys], tuples, s, int(nslots),
                                    htable, nqueues, weights=weights)
+
+
+def backlog(keys, tuples, ticks, drain, htable, nqueues, weights=None, ctx=None):
+    """uint64 peak backlogs ``[len(keys), min(H, Q)]`` of the time-ordered packets ``tuples``
+    under every key (GPU: ``rss_key_search_backlog_device``).  Packet i arrives at tick
+    ``ticks[i]`` (integers in [0, 2^32), non-decreasing) with ``weights[i]`` units (one integer
+    in [0, 2^32) per packet; 1 without ``weights``); every queue drains ``drain`` units (an
+    integer in [0, 2^31)) per tick; a queue's backlog after an arrival is ``max(previous -
+    drain * ticks since, 0) + weight`` and the result is the largest it reaches (0 for a queue
+    without packets).  ``drain=0`` gives the loads of :func:`evaluate`.  IPv4 tuples."""
+    t = _native.tuple_ticks(ticks, len(tuples))
+    drain = _native.backlog_drain(drain)
+    ctx = ctx or _native.default_context()
+    return ctx.key_search_backlog([_native.prepare_key(k) for k in keys], tuples, t, drain,
+                                  htable, nqueues, weights=weights)
 
 
 def peak(loads, htable, nqueues):
@@ -474,6 +496,12 @@ def load_timed_csv(ips_file, time_column, width, weight_column=None):
     return pack_frame(df), weights, slots, nslots
 
 
+def load_ticks(ips_file, time_column, width):
+    """Each row's arrival tick of :func:`load_timed_csv`'s CSV: ``window_slots(times, width)[0]``."""
+    return window_slots(pd.read_csv(ips_file, usecols=[time_column])[time_column].to_numpy(),
+                        width)[0]
+
+
 def load_weighted_csv6(ips_file, column):
     """:func:`load_weighted_csv` for a CSV of IPv6 flows (``TUPLE6_DTYPE`` tuples)."""
     df = pd.read_csv(ips_file)
@@ -541,7 +569,21 @@ def main(argv=None):
                         "window of --window, relative to the busiest window's ideal share")
     p.add_argument("--window", metavar="WIDTH", type=float,
                    help="width of a time window, in the units of --time-column")
+    p.add_argument("--drain", metavar="UNITS", type=int,
+                   help="with --tick: also print each listed key's peak backlog, every queue "
+                        "draining UNITS of load (packets, or --weight-column units) per tick")
+    p.add_argument("--tick", metavar="WIDTH", type=float,
+                   help="width of a --drain tick, in the units of --time-column")
     args = p.parse_args(argv)
+    if (args.drain is None) != (args.tick is None):
+        p.error("--drain and --tick go together: a queue drains --drain units per --tick")
+    if args.drain is not None and args.time_column is None:
+        p.error("--drain and --tick need --time-column (and --window): the backlog takes the "
+                "rows in time order")
+    if args.drain is not None and not 0 <= args.drain < 2**31:
+        p.error("--drain must be an integer in [0, 2^31), got %r" % args.drain)
+    if args.tick is not None and not args.tick > 0:
+        p.error("--tick must be > 0, got %r" % args.tick)
     if (args.time_column is None) != (args.window is None):
         p.error("--time-column and --window go together: the column holds each packet's time, "
                 "the width cuts it into windows")
@@ -635,6 +677,16 @@ def main(argv=None):
                            weights), args.htable_size, args.num_queues)
         for key, value, window in zip(listed, pk["peak"], pk["window"]):
             print("%s  peak %.4f at window %d of %d" % (key_text(key), value, window, nslots))
+        if args.drain is not None:  # the rows in tick order, for this call only
+            try:
+                ticks = load_ticks(args.ips_file, args.time_column, args.tick)
+            except ValueError as err:
+                p.error("--tick %r: %s" % (args.tick, err))
+            order = np.argsort(ticks, kind="stable")
+            peaks = backlog(listed, tuples[order], ticks[order], args.drain, args.htable_size,
+                            args.num_queues, None if weights is None else weights[order])
+            for key, row in zip(listed, peaks):
+                print("%s  backlog %d at queue %d" % (key_text(key), row.max(), row.argmax()))
     if args.out:
         with open(args.out, "w") as f:
             f.write(key_text(ranked[0]["key"]))
